@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- DASP SpMV on MI355X: GFLOP/s and achieved fraction of the HBM roofline.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps, checks the result of the last step against what it must be (all-ones / chained
+  mode below: no second product, no oracle), writes its outputs if --dump-outputs is given and prints the result line.  ms_per_step is
+  the wall time of the K timed steps over K.
+  --full adds everything else this file measures or checks, after the timed region: the separately timed kernel (launch spread, the
+  y-placement candidates), the random-x product against the CPU oracle, the CPU baseline, the device-CSR plan build, the rocSPARSE
+  comparator, the suite of other workloads and precisions, and (N > 1) the step's parts and the other exchange.  --no-suite,
+  --no-cpu-baseline, --no-vendor and --no-random-x leave out single extras of a --full run.
+  --dump-outputs DIR: after the timed steps, y of the last step in natural row order as DIR/y.npy (float64; f16 results as float32).
+  Larger than the dump limit, a fixed seeded sample of rows: DIR/y.npy holds their values, DIR/y_rows.npy their row ids.
   N == 1 : one process, one GPU.
   N  > 1 : one rank per GPU.  Launched by torch.distributed.run (the driver's form) the process IS a rank; launched bare
            (`python bench.py --gpus N`) it starts `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a CHILD
@@ -13,9 +22,9 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
            plane: unique-id broadcast, barriers, max-over-ranks of the time.  Fixed total work => "strong".
 A step is one y = A*x over the whole matrix.  Input: the seeded synthetic stand-in of the SuiteSparse matrix named by
 --workload (no .mtx files / network on the bench machines).  N == 1: values and x all ones as in the reference's driver
-(src/main_f64.cu:131-132), y[i] == nnz(row) checked exactly after the timed region, then ONE more product with seeded random
+(src/main_f64.cu:131-132), y[i] == nnz(row) checked exactly after the timed region, then (--full) ONE more product with seeded random
 values and x on the same full-size matrix, >= 100 k sampled rows compared with the CPU oracle (`verified_random_x`).
-N > 1: a_ij = 0.5 / len(row i), x_0 = 1, so x_t = 2^-t, checked on the gathered y after the timed region, then one product on a
+N > 1: a_ij = 0.5 / len(row i), x_0 = 1, so x_t = 2^-t, checked on the gathered y after the timed region, then (--full) one product on a
 random x checked per rank against the oracle.
 Prints ONE JSON line on rank 0.  The GPU path has no CPU fallback: without a GPU this exits non-zero.
 """
@@ -59,6 +68,8 @@ GATHER_NOTE = "diagnostic only (DESIGN.md 4.6): bounds matrices whose every gath
 TOL = {64: 1e-12, 16: 1e-2}   # BASELINE.json north_star, relative to sum_j |a_ij x_j|
 
 LINE_LIMIT = 4096     # the driver keeps an 8 KB tail of stdout and parses its last line: r04's 22 KB line was lost
+DUMP_LIMIT = 60 << 20   # bytes of array data --dump-outputs writes in all (64 MB at most with the .npy headers)
+DUMP_SEED = 2024        # the row sample of an output larger than that: the same rows in every run
 
 
 def _short(v, n):
@@ -138,6 +149,26 @@ def emit(out):
                 sys.stderr.write("bench.py: could not write %s/bench_suite.json: %s\n" % (d, exc))
     sys.stdout.flush()
     print(driver_line(out), flush=True)
+
+
+def dump_outputs(d, outputs, limit=DUMP_LIMIT):
+    """--dump-outputs: {name: array} -> d/<name>.npy, float64 (float32 for narrower results), so that two builds can be compared output
+    for output.  The arrays share `limit` bytes; one larger than its share is written as the values of a fixed seeded sample of its
+    entries (sorted) beside their indices as d/<name>_rows.npy (float64: exact)."""
+    os.makedirs(d, exist_ok=True)
+    share = limit // max(1, len(outputs))
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32).ravel()
+        rows_path = os.path.join(d, name + "_rows.npy")
+        if a.nbytes > share:
+            k = share // (a.itemsize + 8)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, k, replace=False))
+            np.save(rows_path, rows.astype(np.float64))
+            a = a[rows]
+        elif os.path.exists(rows_path):
+            os.remove(rows_path)                                  # left by an earlier, larger run into the same directory
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 
@@ -316,12 +347,13 @@ def kernel_revision():
     return h.hexdigest()[:12]
 
 
-def choose_y(torch, plan, x, rows, tdt, stats):
+def choose_y(torch, plan, x, rows, tdt, stats, candidates=True):
     """The written vector's placement decides between the two speeds of the HBM-bound kernels (profiles/r04_placement.md).  The run's numbers are taken
     against the FIRST y it allocates -- what a solver calling dasp_plan_spmv with its one y vector gets.  Beside it, for the record
     only: the plan timed against n y vectors of the run's own (2 + 6 launches each) and the fastest of them (`frac_best_of_n_y`).
-    DASP_BENCH_Y_CANDIDATES (default 6; 1: off).  Returns (y, y_best, record): y is the first allocation, y_best the fastest (y itself when off)."""
-    n = max(1, int(os.environ.get("DASP_BENCH_Y_CANDIDATES", "6")))
+    DASP_BENCH_Y_CANDIDATES (default 6; 1: off), `candidates` False: off (a plain run).  Returns (y, y_best, record): y is the first allocation, y_best the
+    fastest (y itself when off)."""
+    n = max(1, int(os.environ.get("DASP_BENCH_Y_CANDIDATES", "6"))) if candidates else 1
     if n == 1 or stats["data_X"] < (256 << 20) or stats["n_col_panels"] or stats["x_window_on"] or stats.get("two_phase"):
         y = torch.zeros(rows, dtype=tdt, device="cuda")
         return y, y, {"y_candidates": 1}
@@ -470,8 +502,9 @@ class Watchdog:
                 os._exit(5)
 
 
-def setup_rank(torch, D, name, scale, prec, rank, world, multi=None, chain=None):
-    """Everything one rank owns.  Single GPU: the plan of the whole matrix (A = 1, x = 1, the reference driver's mode).
+def setup_rank(torch, D, name, scale, prec, rank, world, multi=None, chain=None, full=True):
+    """Everything one rank owns.  Single GPU: the plan of the whole matrix (A = 1, x = 1, the reference driver's mode; `full`: the y-placement
+    candidates of choose_y too).
     Partitioned: its row range (equal nonzeros) as a dasp_mg plan (C ABI) -- a plan over the rank's own columns and one over the
     other ranks' columns remapped into the all-gather layout, the padded y slices and the gather buffer."""
     multi = world > 1 if multi is None else multi                   # the partitioned layout (forced at world 1 by a test hook)
@@ -516,7 +549,7 @@ def setup_rank(torch, D, name, scale, prec, rank, world, multi=None, chain=None)
     plan.drop_host()
     tdt = torch.float64 if prec == 64 else torch.float16
     x = torch.ones(plan.x_len, dtype=tdt, device="cuda")
-    y, y_best, placement = choose_y(torch, plan, x, r1 - r0, tdt, plan.stats)
+    y, y_best, placement = choose_y(torch, plan, x, r1 - r0, tdt, plan.stats, candidates=full)
     arena_trials = int(os.environ.get("DASP_BENCH_ARENA_TRIALS", "0"))          # r3's trials (copies of the whole plan): off unless asked for
     if arena_trials > 1:
         first, kept = plan.tune_placement(arena_trials, x.data_ptr(), y.data_ptr())
@@ -614,12 +647,17 @@ def main():
     ap.add_argument("--workload", default="HV15R")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--precision", type=int, default=64, choices=[64, 16])
-    ap.add_argument("--no-suite", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vendor", action="store_true")
-    ap.add_argument("--no-random-x", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every other measurement and check of this file (see the docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write y of the last timed step to DIR/y.npy")
+    ap.add_argument("--no-suite", action="store_true", help="--full without the suite")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-vendor", action="store_true", help="--full without the rocSPARSE comparator")
+    ap.add_argument("--no-random-x", action="store_true", help="--full without the random-x product against the oracle")
     ap.add_argument("--suite-scale", type=float, default=1.0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)                                         # does not return
@@ -665,7 +703,7 @@ def main():
     vb = prec // 8
     # x_t = c^t must stay a normal number over warmup + steps products: c = 1/2 up to 1000 of them, else 1
     chain = None if args.warmup + args.steps <= 1000 else 1.0
-    R = setup_rank(torch, D, name, scale, prec, rank, world, multi, chain)
+    R = setup_rank(torch, D, name, scale, prec, rank, world, multi, chain, full=full)
     plan, rp, ci, st, pre_s = R["plan"], R["rp"], R["ci"], R["stats"], R["pre_s"]
     rows, cols, nnz_total, lengths = R["rows"], R["cols"], R["nnz_total"], R["lengths"]
     bounds, stride, r0, r1, x, y = R["bounds"], R["stride"], R["r0"], R["r1"], R["x"], R["y"]
@@ -822,7 +860,8 @@ def main():
         except D.DaspError as exc:
             mg_err = str(exc)
 
-    from oracle import oracle as O          # checker / baseline only, after the timed region; never on the measured path
+    if full:
+        from oracle import oracle as O      # checker / baseline only, after the timed region; never on the measured path
     rx = None
     if mg is None:
         # ---- exact check: values and x all ones => y == row length
@@ -831,18 +870,23 @@ def main():
         got_nat = torch.empty_like(got)
         got_nat[torch.from_numpy(plan.order_rid.astype(np.int64)).cuda()] = got
         ok = bool((got_nat == want).all().item()) if prec == 64 else f16_close(torch, got_nat, want)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"y": (got_nat if prec == 64 else got_nat.float()).cpu().numpy()})
     else:
         # ---- chained check: x_t = c^t on every non-empty row (0 on empty ones) after warmup + steps products, on the gathered y
         t_all = args.warmup + args.steps
-        full = mg.get_y().astype(np.float64)
+        gathered = mg.get_y()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"y": gathered})
+        gathered = gathered.astype(np.float64)
         nonempty = (lengths > 0).astype(np.float64)
         if prec == 64:
             want = (R["chain"] ** t_all) * nonempty
-            ok = bool((np.abs(full - want) <= 1e-9 * want).all())
+            ok = bool((np.abs(gathered - want) <= 1e-9 * want).all())
         else:
-            ok = bool(np.isfinite(full).all() and ((full >= 0.5 * nonempty) & (full <= 2.0)).all())
-        ok = ok and bool(np.array_equal(mg.get_y_local().astype(np.float64), full[r0:r1]))
-        if not args.no_random_x:
+            ok = bool(np.isfinite(gathered).all() and ((gathered >= 0.5 * nonempty) & (gathered <= 2.0)).all())
+        ok = ok and bool(np.array_equal(mg.get_y_local().astype(np.float64), gathered[r0:r1]))
+        if full and not args.no_random_x:
             # one more product on a random x (same on every rank): this rank's rows vs the oracle on its CSR slice -- a wrong
             # column id or a misplaced slice of the gathered x cannot hide behind x = const
             dt = np.float64 if prec == 64 else np.float16
@@ -866,7 +910,7 @@ def main():
     # ---- N > 1: what a step is made of, each part alone (events on the launch stream): own-column product, other-column product,
     # the all-gather by itself.  With the overlap a step costs ~ max(own, all-gather) + other; without it their sum.
     parts = None
-    if mg is not None and not host_exchange:
+    if full and mg is not None and not host_exchange:
         tdt = torch.float64 if prec == 64 else torch.float16
         reps = 20
         for _ in range(3):
@@ -892,31 +936,33 @@ def main():
                  "allgather_bytes_per_rank": int(stride * vb), "note": "max over ranks; own-column product = roofline.kernel_ms (rank 0)"}
 
     dog.kick("step parts timed")
-    # ---- dominant kernel alone: HIP events on the launch stream around back-to-back launches
-    k_iters = max(200, min(args.steps, 1000))
-    if mg is None:
-        kx, ky = x, y
-    else:
-        tdt = torch.float64 if prec == 64 else torch.float16
-        kx = torch.ones(plan.x_len, dtype=tdt, device="cuda")
-        ky = torch.zeros(stride, dtype=tdt, device="cuda")
-    kw, ke_sep = plan.time(kx.data_ptr(), ky.data_ptr(), stream, warmup=5, iters=k_iters)      # one event pair around >= 200 back-to-back launches
+    # ---- dominant kernel alone (--full): HIP events on the launch stream around back-to-back launches
     # N = 1: a step IS one launch of the plan (+ stage 2 where long rows were cut), so the kernel's average duration is taken from the driver's own timed region
     # (HIP events on the launch stream around exactly --steps steps) -- the separate >= 200-launch figure stays beside it.
-    # N > 1: the region also holds the exchange, so the dominant kernel (the rank's own-column plan) keeps its separate timing.
-    ke = region_event_ms if mg is None else ke_sep
-    # the spread inside this process: every one of >= 200 launches between its own pair of events (VERDICT r2 weak #8a); each interval
-    # carries the few microseconds an event between two kernels costs, so the headline kernel_ms stays the back-to-back mean above
-    each = np.sort(plan.time_each(kx.data_ptr(), ky.data_ptr(), stream, warmup=5, iters=max(200, k_iters)).astype(np.float64))
-    # the same plan against the FASTEST of the n y vectors this run allocated: for the record only (a solver with one y vector gets `frac`)
-    yb = R.get("y_best")
-    keb = ke_sep if (mg is not None or yb is None or yb is y) else plan.time(x.data_ptr(), yb.data_ptr(), stream, warmup=5, iters=k_iters)[1]
+    # N > 1: the region also holds the exchange, so the dominant kernel (the rank's own-column plan) keeps its separate timing (--full only).
+    ke = region_event_ms if mg is None else None
+    kx = ky = None
+    if full:
+        k_iters = max(200, min(args.steps, 1000))
+        if mg is None:
+            kx, ky = x, y
+        else:
+            tdt = torch.float64 if prec == 64 else torch.float16
+            kx = torch.ones(plan.x_len, dtype=tdt, device="cuda")
+            ky = torch.zeros(stride, dtype=tdt, device="cuda")
+        kw, ke_sep = plan.time(kx.data_ptr(), ky.data_ptr(), stream, warmup=5, iters=k_iters)      # one event pair around >= 200 back-to-back launches
+        ke = region_event_ms if mg is None else ke_sep
+        # the spread inside this process: every one of >= 200 launches between its own pair of events (VERDICT r2 weak #8a); each interval
+        # carries the few microseconds an event between two kernels costs, so the headline kernel_ms stays the back-to-back mean above
+        each = np.sort(plan.time_each(kx.data_ptr(), ky.data_ptr(), stream, warmup=5, iters=max(200, k_iters)).astype(np.float64))
+        # the same plan against the FASTEST of the n y vectors this run allocated: for the record only (a solver with one y vector gets `frac`)
+        yb = R.get("y_best")
+        keb = ke_sep if (mg is not None or yb is None or yb is y) else plan.time(x.data_ptr(), yb.data_ptr(), stream, warmup=5, iters=k_iters)[1]
     R["y_best"] = yb = None
     # partitioned: the dominant kernel is the rank's own-column plan (its x is the rank's own slice)
     nnz_local = int(rp[-1]) if mg is None else mg.nnz_local
     b_alg_local = algorithmic_bytes(r1 - r0, cols if mg is None else (stride if mg.overlap else cols), nnz_local, vb)
     b_alg_total = algorithmic_bytes(rows, cols, nnz_total, vb)
-    achieved = b_alg_local / (ke * 1e6)
     ms_per_step = elapsed * 1e3 / args.steps
     value = 2.0 * nnz_total / (ms_per_step * 1e6)
 
@@ -943,25 +989,30 @@ def main():
                    "row_long": st["row_long"], "row_block": st["row_block"], "rate_fill0": round(st["rate_fill0"], 4),
                    "y_candidates": R.get("placement", {}).get("y_candidates", 0),      # N of roofline.frac_best_of_n_y; `frac` itself is against the first y
                    "placement": R.get("placement", {"y_candidates": 0})},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None,
+        "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", "traffic": None,
                      "kernel": "dasp_spmv_kernel<%s>" % ("double" if prec == 64 else "_Float16"),
-                     "algorithmic_bytes_per_launch": b_alg_local, "kernel_ms": round(ke, 6),
-                     "kernel_ms_separate_launches": round(ke_sep, 6), "frac_separate_launches": round(b_alg_local / (ke_sep * 1e6) / HBM_PEAK_GBPS, 4),
-                     "frac_best_of_n_y": round(b_alg_local / (keb * 1e6) / HBM_PEAK_GBPS, 4), "kernel_ms_best_of_n_y": round(keb, 6),
-                     "launch_ms_min": round(float(each[0]), 6), "launch_ms_p10": round(float(each[len(each) // 10]), 6),
-                     "launch_ms_median": round(float(np.median(each)), 6), "launch_ms_p90": round(float(each[(len(each) * 9) // 10]), 6),
-                     "launch_ms_max": round(float(each[-1]), 6),
-                     "frac_at_fastest_launch": round(b_alg_local / (float(each[0]) * 1e6) / HBM_PEAK_GBPS, 4),
-                     "frac_at_slowest_launch": round(b_alg_local / (float(each[-1]) * 1e6) / HBM_PEAK_GBPS, 4),
-                     "method": ("kernel_ms: hipEvent pair on the launch stream around the driver's %d timed steps (one launch each), against the run's first y; " % args.steps if mg is None else
-                                "kernel_ms: hipEvent pair on the launch stream around %d back-to-back launches of the rank's own-column plan (rank 0 slice); " % k_iters) +
-                               "kernel_ms_separate_launches: a second pair around %d back-to-back launches; launch_ms_*: %d launches with a hipEvent between every two "
-                               "(each interval includes the few us an event between two kernels costs)" % (k_iters, len(each))},
+                     "algorithmic_bytes_per_launch": b_alg_local},
         "achieved_GBps_whole_job": round(b_alg_total / (ms_per_step * 1e6), 1),
         "frac_hbm_roofline_whole_job": round(b_alg_total / (ms_per_step * 1e6) / (HBM_PEAK_GBPS * world), 4),
         "region_event_ms_per_step": round(region_event_ms, 6), "verified": ok, "preprocess_s": round(pre_s, 3),
     }
+    if ke is not None:
+        achieved = b_alg_local / (ke * 1e6)
+        out["roofline"].update(achieved=round(achieved, 1), frac=round(achieved / HBM_PEAK_GBPS, 4), kernel_ms=round(ke, 6),
+                               method="kernel_ms: hipEvent pair on the launch stream around the driver's %d timed steps (one launch each), against the run's first y"
+                               % args.steps if mg is None else
+                               "kernel_ms: hipEvent pair on the launch stream around %d back-to-back launches of the rank's own-column plan (rank 0 slice)" % k_iters)
+    if full:
+        out["roofline"].update({
+            "kernel_ms_separate_launches": round(ke_sep, 6), "frac_separate_launches": round(b_alg_local / (ke_sep * 1e6) / HBM_PEAK_GBPS, 4),
+            "frac_best_of_n_y": round(b_alg_local / (keb * 1e6) / HBM_PEAK_GBPS, 4), "kernel_ms_best_of_n_y": round(keb, 6),
+            "launch_ms_min": round(float(each[0]), 6), "launch_ms_p10": round(float(each[len(each) // 10]), 6),
+            "launch_ms_median": round(float(np.median(each)), 6), "launch_ms_p90": round(float(each[(len(each) * 9) // 10]), 6),
+            "launch_ms_max": round(float(each[-1]), 6),
+            "frac_at_fastest_launch": round(b_alg_local / (float(each[0]) * 1e6) / HBM_PEAK_GBPS, 4),
+            "frac_at_slowest_launch": round(b_alg_local / (float(each[-1]) * 1e6) / HBM_PEAK_GBPS, 4)})
+        out["roofline"]["method"] += ("; kernel_ms_separate_launches: a second pair around %d back-to-back launches; launch_ms_*: %d launches with a hipEvent "
+                                      "between every two (each interval includes the few us an event between two kernels costs)" % (k_iters, len(each)))
     if world == 1 and mg is None:
         out["roofline"].update(traffic_for(name, prec, scale, b_alg_local, kernel_revision()))
     if mg_err is not None:
@@ -979,7 +1030,7 @@ def main():
     # not use is timed here over a shorter chain, so that one record tells the two apart.  Collective: every rank takes the same branches.
     exchange_ms = None
     try:
-        if mg is not None and not host_exchange and cfgs:
+        if full and mg is not None and not host_exchange and cfgs:
             chosen = cfgs[cfg_i]
             exchange_ms = {chosen[0]: {"ms_per_step": round(elapsed * 1e3 / args.steps, 6), "fused": bool(chosen[1]), "steps": args.steps,
                                        "allgather_alone_ms": parts["allgather_alone_ms"] if parts else None}}
@@ -1048,16 +1099,16 @@ def main():
     if exchange_ms is not None:
         out["exchange_ms"] = exchange_ms
 
-    if rank == 0 and world == 1 and mg is None and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and mg is None and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(O, rp, ci, cols)
     if mg is None:
         plan.close()
     del x, y, kx, ky
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and mg is None:
+    if full and rank == 0 and world == 1 and mg is None:
         out.update(device_pre_ms(torch, D, rp, ci, rows, cols, prec))
 
-    if rank == 0 and world == 1 and mg is None and not args.no_random_x:
+    if full and rank == 0 and world == 1 and mg is None and not args.no_random_x:
         try:
             out["verified_random_x"] = verify_random_x(torch, D, O, rp, ci, cols, prec, time_iters=200)
         except Exception as exc:
@@ -1079,7 +1130,7 @@ def main():
 
     dog.partial = out
     dog.kick("headline record complete")
-    if rank == 0 and world == 1 and not multi and not args.no_vendor:
+    if full and rank == 0 and world == 1 and not multi and not args.no_vendor:
         # vendor comparator on the same box and matrix: rocSPARSE CSR SpMV (the reference's cuSPARSE column, main_f64.cu:18-100)
         exe = os.path.join(ROOT, "dasp_amd", "bin", "dasp_rocsparse")
         if prec == 64 and os.path.exists(exe) and not real_matrix(D, name):   # the comparator driver generates the stand-in itself
@@ -1093,7 +1144,7 @@ def main():
             except Exception as exc:
                 out["rocsparse_csr"] = {"error": repr(exc)}
 
-    if rank == 0 and world == 1 and not multi and not args.no_suite:
+    if full and rank == 0 and world == 1 and not multi and not args.no_suite:
         suite = []
         for nm, pr in (("cop20k_A", 64), ("nlpkkt160", 64), ("powerlaw_1M", 64), ("Queen_4147", 64), ("HV15R-unstructured", 64),
                        ("webbase-1M", 16), ("ljournal-2008", 16), ("rmat_2M", 16), ("ljournal-2008-uniform", 16), ("webbase-1M-uniform", 16)):

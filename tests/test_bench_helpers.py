@@ -177,3 +177,36 @@ def test_driver_line_is_short_and_complete(tmp_path, capsys):
     assert json.loads(printed[-1])["value"] == out["value"] and len(printed[-1]) < 4096
     side = json.load(open(tmp_path / "bench_suite.json"))
     assert len(side["suite"]) == len(out["suite"]) and side["roofline"] == out["roofline"]
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_when_too_large(tmp_path):
+    """--dump-outputs: y as <dir>/y.npy in float64 (narrower results as float32); larger than the limit, the values of a fixed seeded
+    sample of rows beside their ids in y_rows.npy -- the same rows in every run, and no stale ids left by an earlier larger dump"""
+    b = _bench()
+    y64 = np.arange(1000, dtype=np.float64) * 0.5
+    b.dump_outputs(str(tmp_path / "a"), {"y": y64})
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y64) and not (tmp_path / "a" / "y_rows.npy").exists()
+    y16 = np.array([1.0, 65504.0, np.inf, 0.25], np.float16)
+    b.dump_outputs(str(tmp_path / "h"), {"y": y16})
+    got = np.load(tmp_path / "h" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y16.astype(np.float32))
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), {"y": y64}, limit=1600)          # 100 rows of 8 + 8 bytes
+    rows = np.load(tmp_path / "s1" / "y_rows.npy")
+    vals = np.load(tmp_path / "s1" / "y.npy")
+    assert rows.dtype == np.float64 and vals.dtype == np.float64 and rows.size == vals.size == 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(vals, y64[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "y_rows.npy")) and np.array_equal(vals, np.load(tmp_path / "s2" / "y.npy"))
+    b.dump_outputs(str(tmp_path / "s1"), {"y": y64})                        # the same directory, now under the limit
+    assert not (tmp_path / "s1" / "y_rows.npy").exists() and np.array_equal(np.load(tmp_path / "s1" / "y.npy"), y64)
+
+
+def test_bench_options_and_steps_check():
+    """--full and --dump-outputs are options of the command line; --steps below 1 is a usage error before anything touches a GPU"""
+    import subprocess
+    import sys
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

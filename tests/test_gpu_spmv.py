@@ -265,13 +265,43 @@ def test_bench_reads_real_matrices_from_dasp_mtx_dir(dasp, torch_cuda, tmp_path)
     env = dict(os.environ, DASP_MTX_DIR=str(tmp_path))
     out = None
     for run in range(2):                                   # second run: from the binary CSR cache written by the first
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-suite", "--no-vendor",
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-suite", "--no-vendor",
                             "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
         out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
         assert out["data"] == "suitesparse" and out["verified"] is True and out["verified_random_x"]["ok"] is True
         assert out["config"]["rows"] == rows and out["config"]["nnz"] == ci.size and "DASP_MTX_DIR" in out["config"]["workload"]
     assert (tmp_path / "HV15R.mtx.f64.csrbin").exists()
+
+
+@pytest.mark.parametrize("prec", [64, 16])
+def test_bench_plain_run_times_its_steps_and_dumps_y(dasp, torch_cuda, tmp_path, prec):
+    """A plain `bench.py` run: the headline keys, exactly --steps timed steps, none of the --full extras, and --dump-outputs writes y of
+    the last step in natural row order (all-ones mode: y == row lengths), identical from run to run"""
+    import json
+    import sys
+    lens = dasp.synth_row_lengths("HV15R", 0.02).astype(np.float64)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--scale", "0.02",
+                            "--precision", str(prec), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = json.loads(r.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 7 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["verified"] is True
+        assert out["unit"] == "GFLOP/s" and out["higher_is_better"] is True and out["metric"].startswith("SpMV GFLOP/s")
+        assert out["roofline"]["kernel_ms"] > 0 and out["config"]["y_candidates"] == 1
+        for k in ("cpu_baseline", "verified_random_x", "rocsparse_csr_ms", "suite_errors", "pre_ms_device_csr"):
+            assert k not in out, k
+        assert "frac_separate_launches" not in out["roofline"] and "suite_frac" not in out["roofline"]
+        y = np.load(d / "y.npy")
+        assert y.dtype == (np.float64 if prec == 64 else np.float32) and y.shape == lens.shape and not (d / "y_rows.npy").exists()
+        if prec == 64:
+            np.testing.assert_array_equal(y, lens)
+        else:
+            assert (np.abs(y - lens) <= 1e-2 * np.maximum(lens, 1)).all()
+        dumps.append(y)
+    np.testing.assert_array_equal(dumps[0], dumps[1])
 
 
 @pytest.mark.parametrize("prec", [64, 16])
@@ -1288,7 +1318,7 @@ def test_bench_multi_rank_flow_on_one_gpu(torch_cuda, exchange):
     import json
     import sys
     env = dict(os.environ, DASP_BENCH_SHARE_GPU="1", DASP_BENCH_EXCHANGE=exchange)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "5", "--warmup", "2",
                         "--scale", "0.02"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = r.stdout.strip().splitlines()[-1]              # the driver parses the LAST line, and keeps an 8 KB tail
@@ -1313,7 +1343,7 @@ def test_bench_rccl_calls_run_at_world_size_one(torch_cuda):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, DASP_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2",
                         "--scale", "0.02", "--no-suite", "--no-cpu-baseline", "--no-vendor"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -3,15 +3,18 @@
 #   smoke | full -m gpu suite | PMC traffic of every workload (tools/traffic_all.sh -> profiles/traffic.json at this kernel revision) | bench.py as the driver runs it
 #   (compact line + bench_suite.json) | rocprofv3 --kernel-trace --stats of the bench command | MFMA / occupancy counters of four workloads (tools/pmc.sh)
 export ROUND=${ROUND:-r06}
+# OUT (set by the caller, no default): the directory the other steps of this batch write to; the bench lines below write there too
+OUT=$(cd "${OUT:?set OUT to the output directory of this batch}" && pwd) || exit 1
+root=$PWD
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 python -m pytest tests -m gpu -x -q > gpurun_out/round_end_tests.log 2>&1; grep -E "passed|failed" gpurun_out/round_end_tests.log | tail -1
 bash tools/traffic_all.sh > gpurun_out/round_end_traffic.log 2>&1
 python tools/traffic_collect.py > gpurun_out/round_end_traffic_collect.log 2>&1 && cp profiles/traffic.json gpurun_out/round_end_traffic.json && cp profiles/${ROUND}_traffic.md gpurun_out/round_end_traffic.md
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/round_end_bench.json.log 2> gpurun_out/round_end_bench.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT"/round_end_bench.json.log 2> "$OUT"/round_end_bench.err
 cp gpurun_out/bench_suite.json gpurun_out/round_end_bench_suite.json
 export TMPDIR=/tmp
 rm -rf gpurun_out/round_end_prof
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/round_end_prof -- python3 $GRAFT_REPO_ROOT/bench.py --no-suite --no-vendor --steps 20 > $GRAFT_REPO_ROOT/gpurun_out/round_end_prof.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT"/round_end_prof -- python3 "$root"/bench.py --full --no-suite --no-vendor --steps 20 > "$OUT"/round_end_prof.log 2>&1)
 cp gpurun_out/bench_suite.json gpurun_out/round_end_prof_suite.json
 # MFMA utilisation (north_star): one counter group per pass, the program itself after --
 B=dasp_amd/bin/dasp_bench
