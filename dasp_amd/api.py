@@ -87,7 +87,7 @@ class Plan:
     def __init__(self, csrRowPtr, csrColIdx, csrVal, colA, precision=64, threshold=0.75, block_longest=256,
                  y_order=Y_PERMUTED, long_piece=0, host_threads=0, part_bounds=None, part_stride=0, x_window=0, row_window=0, cid16=0, stream_policy=0,
                  col_panels=0, slab_max_len=0, x_window_hybrid=0, piece_min_len=0, chunk_pairs=0, cid8=0, short_seg=0, row_tile_max=0, sort_columns=0,
-                 two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0):
+                 two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0, value_map=0):
         L = _lib.lib()
         self.precision = precision
         dt = _dtype(precision)
@@ -103,6 +103,7 @@ class Plan:
         opt.col_panels, opt.slab_max_len, opt.x_window_hybrid, opt.piece_min_len = col_panels, slab_max_len, x_window_hybrid, piece_min_len
         opt.chunk_pairs, opt.cid8, opt.short_seg, opt.row_tile_max, opt.sort_columns = chunk_pairs, cid8, short_seg, row_tile_max, sort_columns
         opt.two_phase, opt.tp_col_block, opt.tp_row_block, opt.long_cb = two_phase, tp_col_block, tp_row_block, long_cb
+        opt.value_map = value_map
         self._pb = None
         if part_bounds is not None:
             self._pb = np.ascontiguousarray(part_bounds, np.int32)
@@ -117,7 +118,8 @@ class Plan:
     @classmethod
     def from_device(cls, d_row_ptr, d_col_idx, d_val, rowA, colA, nnzA, precision=64, threshold=0.75, block_longest=256,
                     y_order=Y_PERMUTED, long_piece=0, part_bounds=None, part_stride=0, x_window=0, row_window=0, cid16=0, col_panels=0, slab_max_len=0,
-                    x_window_hybrid=0, piece_min_len=0, chunk_pairs=0, cid8=0, short_seg=0, row_tile_max=0, sort_columns=0, two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0):
+                    x_window_hybrid=0, piece_min_len=0, chunk_pairs=0, cid8=0, short_seg=0, row_tile_max=0, sort_columns=0, two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0,
+                    value_map=0):
         """Plan from a CSR that already lives on the GPU (integer device addresses): packed by kernels, comes back uploaded."""
         L = _lib.lib()
         self = cls.__new__(cls)
@@ -129,6 +131,7 @@ class Plan:
         opt.slab_max_len, opt.x_window_hybrid, opt.piece_min_len = slab_max_len, x_window_hybrid, piece_min_len
         opt.chunk_pairs, opt.cid8, opt.short_seg, opt.row_tile_max, opt.sort_columns = chunk_pairs, cid8, short_seg, row_tile_max, sort_columns
         opt.two_phase, opt.tp_col_block, opt.tp_row_block, opt.long_cb = two_phase, tp_col_block, tp_row_block, long_cb
+        opt.value_map = value_map
         self._pb = None
         if part_bounds is not None:
             self._pb = np.ascontiguousarray(part_bounds, np.int32)
@@ -204,6 +207,8 @@ class Plan:
             _lib.check(int(n))
         if name in ("med_cid16", "long_cid16", "rt_start", "tp_lrow", "tp_lcol", "lcb_lcol"):
             dt = np.uint16
+        elif name.endswith("_val_map"):
+            dt = np.uint32
         elif name == "rt_mask":
             dt = np.uint64
         elif name == "med_cid8":
@@ -232,6 +237,28 @@ class Plan:
 
     def drop_host(self):
         _lib.check(_lib.lib().dasp_plan_drop_host(self._h))
+
+    # -- new values, same pattern (value_map=1) ---------------------------------------
+    def update_values(self, csrVal):
+        """New host values (nnzA, the CSR order the plan was created from): host arrays rewritten, an uploaded plan's device arrays too
+        (dasp_plan_update_values_host; synchronises)."""
+        v = np.ascontiguousarray(csrVal, _dtype(self.precision))
+        if v.size != self.nnzA:
+            raise ValueError("update_values: %d values for a plan of %d nonzeros" % (v.size, self.nnzA))
+        _lib.check(_lib.lib().dasp_plan_update_values_host(self._h, _vp(v)))
+
+    def update_values_device(self, d_val, stream=0):
+        """New device values (integer address of nnzA values of the plan's precision): one kernel launch on `stream`, ordered with
+        the SpMVs on it (dasp_plan_update_values); drops the host copies of the packed arrays."""
+        _lib.check(_lib.lib().dasp_plan_update_values(self._h, C.c_void_p(d_val), C.c_void_p(stream)))
+
+    @property
+    def value_map_slots(self):
+        """Mapped value slots over all value arrays (panels included); 0 without a map."""
+        n = int(_lib.lib().dasp_plan_value_map_slots(self._h))
+        if n < 0:
+            _lib.check(n)
+        return n
 
     def set_stream_policy(self, policy):
         """0 auto, 1 plain loads (reference dasp_spmv), 2 non-temporal loads (reference dasp_spmv2 'bypass')."""

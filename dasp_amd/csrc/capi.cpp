@@ -101,6 +101,7 @@ static int normalise_options(Plan &p, const dasp_options_t *opt, int colA)
             }
         p.opt.part_bounds = p.part_bounds.data();
     } else { p.opt.n_parts = 0; p.opt.part_bounds = nullptr; }
+    if (p.opt.value_map != 0 && p.opt.value_map != 1) { set_error("value_map must be 0 or 1"); return DASP_ERR_ARG; }
     return DASP_OK;
 }
 
@@ -223,7 +224,8 @@ static long long host_array_impl(const dasp_plan_t *plan, const char *name, cons
     // the nnz-sized arrays exist on the host only until dasp_plan_drop_host (never, for a plan packed on the device);
     // the O(rows) arrays and order_rid always do
     static const char *const kBulk[] = {"long_val", "long_cid", "long_cid16", "med_val", "med_cid", "med_cid16", "med_cid8", "irr_val", "irr_cid", "short_val", "short_cid", "rt_val", "rt_cid",
-                                        "tp_val", "tp_lrow", "tp_lcol", "tp_dst", "lcb_val", "lcb_lcol"};
+                                        "tp_val", "tp_lrow", "tp_lcol", "tp_dst", "lcb_val", "lcb_lcol",
+                                        "long_val_map", "med_val_map", "irr_val_map", "short_val_map", "rt_val_map", "tp_val_map", "lcb_val_map"};
     if (p.host_dropped)
         for (const char *b : kBulk)
             if (std::strcmp(name, b) == 0) { set_error("host copy of this array was dropped (use dasp_plan_download_array)"); return DASP_ERR_STATE; }
@@ -233,6 +235,15 @@ static long long host_array_impl(const dasp_plan_t *plan, const char *name, cons
     auto rints = [&](const raw_vector<int> &v) { *ptr = v.data(); *elem_bytes = 4; return (long long)v.size(); };
     const std::string n(name);
     if (n == "order") return ints(p.order);
+    // value maps (opt.value_map): one uint32 per slot of the value array, 1 + the caller's CSR index, 0 = pad; empty without a map
+    auto maps = [&](const std::vector<uint32_t> &v) { *ptr = v.data(); *elem_bytes = 4; return (long long)v.size(); };
+    if (n == "long_val_map") return maps(p.long_map);
+    if (n == "med_val_map") return maps(p.med_map);
+    if (n == "irr_val_map") return maps(p.irr_map);
+    if (n == "short_val_map") return maps(p.short_map);
+    if (n == "rt_val_map") return maps(p.rt_map);
+    if (n == "tp_val_map") return maps(p.tp.map);
+    if (n == "lcb_val_map") return maps(p.lcb.map);
     if (n == "dst_map") return ints(p.dst_map);
     if (n == "long_val") return vals(p.long_val);
     if (n == "long_cid") return rints(p.long_cid);
@@ -322,6 +333,7 @@ int dasp_plan_drop_host(dasp_plan_t *plan)
     dropc(p.irr_val); dropi(p.irr_cid); dropc(p.short_val); dropi(p.short_cid); dropc(p.rt_val); dropi(p.rt_cid);
     dropc(p.lcb.val); raw_vector<uint16_t>().swap(p.lcb.lcol);
     dropc(p.tp.val); raw_vector<uint16_t>().swap(p.tp.lrow); raw_vector<uint16_t>().swap(p.tp.lcol); std::vector<int>().swap(p.tp.dst);
+    for (auto *m : {&p.long_map, &p.med_map, &p.irr_map, &p.short_map, &p.rt_map, &p.tp.map, &p.lcb.map}) std::vector<uint32_t>().swap(*m);      // (the device maps stay)
     p.host_dropped = true;
     for (auto &h : p.panels) if (int rc = dasp_plan_drop_host(h.get())) return rc;
     return DASP_OK;

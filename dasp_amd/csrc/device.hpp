@@ -111,7 +111,19 @@ struct DevicePlan {
     int device = -1;
     // column-panel parent: arena = the panels' partial results, panel k at ypart + k * ypart_stride elements
     size_t ypart_stride = 0;
+    // value map (Plan::value_map; devpack.hip dasp_value_refresh_kernel), top-level plans only: the maps of every value array of the plan, its panels,
+    // column-blocked long rows and two-phase streams in ONE allocation of their own (not in the arena: an arena is byte-identical with or without
+    // a map), and a table of runs {arena, destination offset from that arena's base, map offset, count}.  vm_arenas[i] = the plan whose arena run
+    // index i writes into; its base is read at every launch, so that an arena moved by the placement trials is still found.
+    void *vm_map = nullptr, *vm_runs = nullptr;
+    bool vm_ready = false;          // the table is complete (a failed map upload leaves it false: dasp_plan_update_values refuses the plan)
+    void *pk_map[5] = {};           // device-built plans: the packers' maps of long / med / irr / short / rt values, until value_map_upload gathers them
+    int vm_n_runs = 0;
+    long long vm_blocks = 0, vm_slots = 0;
+    std::vector<Plan *> vm_arenas;
 };
+int value_map_upload(Plan &p);         // devpack.hip: the device maps + run table of an uploaded top-level plan that carries host maps
+void value_map_free(DevicePlan *d);    // devpack.hip
 
 
 int require_device();                  // upload.cpp: DASP_OK, or DASP_ERR_NO_DEVICE with the error text set

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device.hpp"
@@ -119,9 +120,17 @@ __global__ void k_chunk_spans(const int *rp, const int *ci, const int *ridM, con
     if (lane == 0) { k16[b] = out; if (narrow) narrow[b] = mask; }
 }
 
+// value map entry of nonzero j of a device CSR (DevCsr::src; nullptr: the caller's own CSR, entry = j + 1)
+__device__ __forceinline__ unsigned map_of(const unsigned *src, long long j) { return src ? src[j] : (unsigned)(j + 1); }
+// 1 + index: the map entries of a CSR that is the caller's own (the input of a device column sort)
+__global__ void k_iota1(unsigned *out, long long n)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = (unsigned)(i + 1);
+}
+
 template <class T>
 __global__ void k_pack_long(const int *rp, const int *ci, const T *val, const int *ridL, const long long *startL, int nlong, RemapDev remap,
-                            T *lv, int *lc)
+                            T *lv, int *lc, const unsigned *src, unsigned *lm /* value map, nullptr: none */)
 {
     const int lane = threadIdx.x & 63, i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= nlong) return;
@@ -131,6 +140,7 @@ __global__ void k_pack_long(const int *rp, const int *ci, const T *val, const in
         const bool in = j < len;
         lv[at + j] = in ? val[a0 + j] : (T)0;
         lc[at + j] = in ? remap(ci[a0 + j]) : -1;
+        if (lm) lm[at + j] = in ? map_of(src, a0 + j) : 0u;
     }
 }
 
@@ -161,7 +171,8 @@ template <class T, bool C16>
 __global__ void k_pack_medium(const int *rp, const int *ci, const T *val, const int *ridM, const int *lenM, const int *med_ptr,
                               const int *irr_ptr, int nmed, int nb, RemapDev remap, T *mv, int *mc, unsigned short *mc16, int *mbase,
                               T *iv, int *ic, int pair_mode, const int *c8ptr, unsigned char *mc8, int *korig,
-                              const int *win_cmin, const int *win_len, int bpw /* blocks per window; 0: per-chunk bases (Plan::win_rel16 off) */)
+                              const int *win_cmin, const int *win_len, int bpw /* blocks per window; 0: per-chunk bases (Plan::win_rel16 off) */,
+                              const unsigned *src, unsigned *mm, unsigned *im /* value maps of med / irr, nullptr: none */)
 {
     constexpr int K = sizeof(T) == 8 ? 4 : 16, CH = kMedRows * K, VPL = CH / 64;
     const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -178,7 +189,7 @@ __global__ void k_pack_medium(const int *rp, const int *ci, const T *val, const 
     int n8 = 0, a8 = 0, a16 = 0; size_t e8 = 0, e16 = (size_t)c0 * CH;
     if constexpr (C16) { n8 = c8ptr[b + 1] - c8ptr[b]; e8 = (size_t)c8ptr[b] * CH; e16 = ((size_t)c0 - (size_t)c8ptr[b]) * CH; }
     for (int c = 0; c < nc; ++c) {
-        int col[VPL]; T v[VPL];
+        int col[VPL]; T v[VPL]; unsigned ms[VPL];
         int lo = 2147483647, hi = -1;
 #pragma unroll
         for (int q = 0; q < VPL; ++q) {
@@ -187,6 +198,7 @@ __global__ void k_pack_medium(const int *rp, const int *ci, const T *val, const 
             const bool in = row_ok && i < len;
             v[q] = in ? val[a0 + i] : (T)0;
             col[q] = in ? remap(ci[a0 + i]) : -1;
+            ms[q] = in && mm ? map_of(src, a0 + i) : 0u;
             if (in) { lo = min(lo, col[q]); hi = max(hi, col[q]); }
         }
         if constexpr (C16) {
@@ -200,26 +212,30 @@ __global__ void k_pack_medium(const int *rp, const int *ci, const T *val, const 
 #pragma unroll
             for (int q = 0; q < VPL; ++q) {
                 mv[at + q] = v[q];
+                if (mm) mm[at + q] = ms[q];
                 if (pos < n8) mc8[e8 + med_cid8_index(pos, lane, CH, oneshot)] = col[q] < 0 ? (unsigned char)0xFF : (unsigned char)(col[q] - lo);      // f64 only: VPL = 1
                 else mc16[e16 + med_elem_index(npair - n8, pos - n8, lane, q, VPL, CH)] = col[q] < 0 ? (unsigned short)0xFFFF : (unsigned short)(col[q] - lo);
             }
         } else {
             const size_t at = (size_t)c0 * CH + med_elem_index(npair, c, lane, 0, VPL, CH);
 #pragma unroll
-            for (int q = 0; q < VPL; ++q) { mv[at + q] = v[q]; mc[at + q] = col[q]; }
+            for (int q = 0; q < VPL; ++q) { mv[at + q] = v[q]; mc[at + q] = col[q]; if (mm) mm[at + q] = ms[q]; }
         }
     }
     // irregular tail = the LAST tl entries of the row (dasp_f64.h:1094-1106); lanes kq = 0..3 of a row share the copy
     if (row_ok) {
         const int t0 = irr_ptr[r], tl = irr_ptr[r + 1] - t0;
-        for (int j = kq; j < tl; j += 4) { iv[t0 + j] = val[a0 + len - tl + j]; ic[t0 + j] = remap(ci[a0 + len - tl + j]); }
+        for (int j = kq; j < tl; j += 4) {
+            iv[t0 + j] = val[a0 + len - tl + j]; ic[t0 + j] = remap(ci[a0 + len - tl + j]);
+            if (im) im[t0 + j] = map_of(src, a0 + len - tl + j);
+        }
     }
 }
 
 // short slabs: one thread per (slab position, k); positions past the slab's row count are pads
 template <class T>
 __global__ void k_pack_short(const int *rp, const int *ci, const T *val, const int *list, int count, int tiles, int L, long long elem_off,
-                             int SR, int seg, RemapDev remap, T *sv, int *sc)
+                             int SR, int seg, RemapDev remap, T *sv, int *sc, const unsigned *src, unsigned *sm /* value map, nullptr: none */)
 {
     const long long n = (long long)tiles * short_tile_elems(seg != 0, L, SR);
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
@@ -238,6 +254,7 @@ __global__ void k_pack_short(const int *rp, const int *ci, const T *val, const i
         const int a0 = in ? rp[list[t]] : 0;
         sv[elem_off + e] = in ? val[a0 + k] : (T)0;
         sc[elem_off + e] = in ? remap(ci[a0 + k]) : -1;
+        if (sm) sm[elem_off + e] = in ? map_of(src, a0 + k) : 0u;
     }
 }
 
@@ -378,12 +395,23 @@ static int pack_all_typed(Plan &p, const DevCsr &d, const PackMeta &m)
     const T *val = static_cast<const T *>(d.val);
     RemapHolder rm; if (int rc = rm.init(p)) return rc;
     const int nlong = (int)m.ridL->size(), nmed = (int)m.ridM->size(), nb = (nmed + kMedRows - 1) / kMedRows;
+    // value map (opt.value_map): the packers write it beside the values, into buffers of the plan's own until value_map_upload gathers them
+    const unsigned *src = d.src;
+    unsigned *pm[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (p.value_map) {
+        const size_t cnt[4] = {p.cnt_long, p.cnt_reg, p.cnt_irr, p.cnt_short};
+        for (int a = 0; a < 4; ++a) {
+            if (cnt[a] == 0) continue;
+            HIP_TRYP(hipMalloc(&dp.pk_map[a], cnt[a] * 4));
+            pm[a] = static_cast<unsigned *>(dp.pk_map[a]);
+        }
+    }
     if (nlong > 0) {
         DevVec<int> dr; DevVec<long long> ds;
         if (int rc = dr.init(*m.ridL)) return rc;
         if (int rc = ds.init(*m.startL)) return rc;
         hipLaunchKernelGGL((k_pack_long<T>), dim3(waves_grid(nlong)), dim3(256), 0, 0, d.rp, d.ci, val, dr.d, ds.d, nlong, rm.r,
-                           reinterpret_cast<T *>(base + dp.map.long_val), reinterpret_cast<int *>(base + dp.map.long_cid));
+                           reinterpret_cast<T *>(base + dp.map.long_val), reinterpret_cast<int *>(base + dp.map.long_cid), src, pm[0]);
         HIP_TRYP(hipGetLastError());
         const int np = (int)p.piece_dst.size();
         if (np > 0) {
@@ -410,10 +438,10 @@ static int pack_all_typed(Plan &p, const DevCsr &d, const PackMeta &m)
         if (p.cid16)
             hipLaunchKernelGGL((k_pack_medium<T, true>), dim3(waves_grid(nb)), dim3(256), 0, 0, d.rp, d.ci, val, dr.d, dl.d, dp.args.med_ptr,
                                dp.args.irr_ptr, nmed, nb, rm.r, mv, mc, mc16, mb, iv, ic, p.pair_mode, dp.args.med_c8ptr, mc8, dko.d,
-                               dp.args.win_cmin, dp.args.win_len, p.win_rel16 ? p.row_window / kMedRows : 0);
+                               dp.args.win_cmin, dp.args.win_len, p.win_rel16 ? p.row_window / kMedRows : 0, src, pm[1], pm[2]);
         else
             hipLaunchKernelGGL((k_pack_medium<T, false>), dim3(waves_grid(nb)), dim3(256), 0, 0, d.rp, d.ci, val, dr.d, dl.d, dp.args.med_ptr,
-                               dp.args.irr_ptr, nmed, nb, rm.r, mv, mc, mc16, mb, iv, ic, p.pair_mode, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+                               dp.args.irr_ptr, nmed, nb, rm.r, mv, mc, mc16, mb, iv, ic, p.pair_mode, nullptr, nullptr, nullptr, nullptr, nullptr, 0, src, pm[1], pm[2]);
         HIP_TRYP(hipGetLastError());
         HIP_TRYP(hipDeviceSynchronize());
         if (p.cid16 && !p.med_korig.empty()) HIP_TRYP(hipMemcpy(p.med_korig.data(), dko.d, p.med_korig.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -426,7 +454,7 @@ static int pack_all_typed(Plan &p, const DevCsr &d, const PackMeta &m)
         const long long n = (long long)G.tiles * short_tile_elems(G.seg != 0, G.len, p.geo.short_rows);
         hipLaunchKernelGGL((k_pack_short<T>), dim3((unsigned)std::min<long long>((n + 255) / 256, 65535)), dim3(256), 0, 0, d.rp, d.ci, val,
                            dl.d, G.count, G.tiles, G.len, G.elem_off, p.geo.short_rows, G.seg, rm.r,
-                           reinterpret_cast<T *>(base + dp.map.short_val), reinterpret_cast<int *>(base + dp.map.short_cid));
+                           reinterpret_cast<T *>(base + dp.map.short_val), reinterpret_cast<int *>(base + dp.map.short_cid), src, pm[3]);
         HIP_TRYP(hipGetLastError());
         HIP_TRYP(hipDeviceSynchronize());
     }
@@ -461,7 +489,7 @@ __global__ void k_panel_count(const int *rp, const int *ci, int m, RemapDev rema
 }
 template <class T>
 __global__ void k_panel_scatter(const int *rp, const int *ci, const T *val, int m, RemapDev remap, const int *bnd, int P,
-                                const int *rpP /* [P][m + 1], scanned */, int *const *ciP, T *const *valP)
+                                const int *rpP /* [P][m + 1], scanned */, int *const *ciP, T *const *valP, const unsigned *src, unsigned *const *srcP /* nullptr: no map */)
 {
     const int lane = threadIdx.x & 63, i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= m) return;
@@ -480,7 +508,7 @@ __global__ void k_panel_scatter(const int *rp, const int *ci, const T *val, int 
             if (k == q) at = base + __popcll(mask & below);
             if (lane == q) cursor += __popcll(mask);
         }
-        if (in) { ciP[k][at] = c; valP[k][at] = val[j]; }
+        if (in) { ciP[k][at] = c; valP[k][at] = val[j]; if (srcP) srcP[k][at] = map_of(src, j); }
     }
 }
 
@@ -535,27 +563,32 @@ int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &
     }
     std::vector<int *> h_ci((size_t)P, nullptr);
     std::vector<void *> h_val((size_t)P, nullptr);
+    std::vector<unsigned *> h_src((size_t)P, nullptr);
     out.assign((size_t)P, DevCsr{nullptr, nullptr, nullptr});
     for (int k = 0; k < P; ++k) {
         const size_t nk = (size_t)rpP_host[(size_t)k][(size_t)m];
-        void *a = nullptr, *b = nullptr;
+        void *a = nullptr, *b = nullptr, *c = nullptr;
         if (int rc = dmalloc(nk * sizeof(int), &a)) return rc;
         if (int rc = dmalloc(nk * vb, &b)) return rc;
-        h_ci[(size_t)k] = static_cast<int *>(a); h_val[(size_t)k] = b;
-        out[(size_t)k] = DevCsr{static_cast<const int *>(cnt) + (size_t)k * row, static_cast<const int *>(a), b};
+        if (p.value_map) if (int rc = dmalloc(nk * 4, &c)) return rc;      // the caller's nonzero of every panel entry (value map)
+        h_ci[(size_t)k] = static_cast<int *>(a); h_val[(size_t)k] = b; h_src[(size_t)k] = static_cast<unsigned *>(c);
+        out[(size_t)k] = DevCsr{static_cast<const int *>(cnt) + (size_t)k * row, static_cast<const int *>(a), b, static_cast<const uint32_t *>(c)};
     }
-    void *pc = nullptr, *pv = nullptr;
+    void *pc = nullptr, *pv = nullptr, *ps = nullptr;
     if (int rc = dmalloc((size_t)P * sizeof(void *), &pc)) return rc;
     if (int rc = dmalloc((size_t)P * sizeof(void *), &pv)) return rc;
+    if (int rc = dmalloc((size_t)P * sizeof(void *), &ps)) return rc;
     HIP_TRYP(hipMemcpy(pc, h_ci.data(), (size_t)P * sizeof(void *), hipMemcpyHostToDevice));
     HIP_TRYP(hipMemcpy(pv, h_val.data(), (size_t)P * sizeof(void *), hipMemcpyHostToDevice));
+    HIP_TRYP(hipMemcpy(ps, h_src.data(), (size_t)P * sizeof(void *), hipMemcpyHostToDevice));
+    unsigned *const *srcP = p.value_map ? static_cast<unsigned *const *>(ps) : nullptr;
     if (m > 0) {
         if (p.precision == 64)
             hipLaunchKernelGGL((k_panel_scatter<double>), dim3(waves_grid(m)), dim3(256), 0, 0, d.rp, d.ci, static_cast<const double *>(d.val), m, rm.r, dbnd.d, P,
-                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<double *const *>(pv));
+                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<double *const *>(pv), d.src, srcP);
         else
             hipLaunchKernelGGL((k_panel_scatter<_Float16>), dim3(waves_grid(m)), dim3(256), 0, 0, d.rp, d.ci, static_cast<const _Float16 *>(d.val), m, rm.r, dbnd.d, P,
-                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<_Float16 *const *>(pv));
+                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<_Float16 *const *>(pv), d.src, srcP);
     }
     HIP_TRYP(hipGetLastError());
     HIP_TRYP(hipDeviceSynchronize());
@@ -604,8 +637,24 @@ int devpack_sort_columns(const Plan &p, const DevCsr &d, std::vector<std::shared
     if (vb == 8) e = hipcub::DeviceSegmentedSort::StableSortPairs(tmp, tmp_bytes, d.ci, static_cast<int *>(ci2), static_cast<const unsigned long long *>(d.val), static_cast<unsigned long long *>(val2), nnz, m, d.rp, d.rp + 1);
     else e = hipcub::DeviceSegmentedSort::StableSortPairs(tmp, tmp_bytes, d.ci, static_cast<int *>(ci2), static_cast<const unsigned short *>(d.val), static_cast<unsigned short *>(val2), nnz, m, d.rp, d.rp + 1);
     if (e != hipSuccess) { set_error("hipcub segmented sort (sort_columns)"); return DASP_ERR_HIP; }
+    void *src2 = nullptr;
+    if (p.value_map) {      // the map entries ride through the same stable sort (same keys: the same permutation)
+        void *src1 = nullptr, *ci3 = nullptr;
+        if (int rc = dmalloc((size_t)nnz * 4, &src1)) return rc;
+        if (int rc = dmalloc((size_t)nnz * 4, &src2)) return rc;
+        if (int rc = dmalloc((size_t)nnz * 4, &ci3)) return rc;
+        if (d.src) HIP_TRYP(hipMemcpy(src1, d.src, (size_t)nnz * 4, hipMemcpyDeviceToDevice));
+        else hipLaunchKernelGGL(k_iota1, dim3((unsigned)std::min<long long>(4096, ((long long)nnz + 255) / 256)), dim3(256), 0, 0, static_cast<unsigned *>(src1), (long long)nnz);
+        HIP_TRYP(hipGetLastError());
+        size_t tb2 = 0;
+        if (hipcub::DeviceSegmentedSort::StableSortPairs(nullptr, tb2, d.ci, static_cast<int *>(ci3), static_cast<const unsigned *>(src1), static_cast<unsigned *>(src2), nnz, m, d.rp, d.rp + 1) != hipSuccess ||
+            (tb2 > tmp_bytes && dmalloc(tb2, &tmp) != DASP_OK) ||
+            hipcub::DeviceSegmentedSort::StableSortPairs(tmp, tb2 = std::max(tb2, tmp_bytes), d.ci, static_cast<int *>(ci3), static_cast<const unsigned *>(src1), static_cast<unsigned *>(src2), nnz, m, d.rp, d.rp + 1) != hipSuccess) {
+            set_error("hipcub segmented sort (sort_columns, value map)"); return DASP_ERR_HIP;
+        }
+    }
     HIP_TRYP(hipDeviceSynchronize());
-    *out = DevCsr{d.rp, static_cast<const int *>(ci2), val2};
+    *out = DevCsr{d.rp, static_cast<const int *>(ci2), val2, static_cast<const uint32_t *>(src2)};
     *did = 1;
     return DASP_OK;
 }
@@ -613,7 +662,8 @@ int devpack_sort_columns(const Plan &p, const DevCsr &d, std::vector<std::shared
 // ---- row tiles of a column panel (plan.cpp build_panels): one wave per row moves the row either into the tiles' arrays or into the
 // sub-matrix of the rows that stay with the panel's plan; a row's elements keep their order
 template <class T>
-__global__ void k_row_tiles_move(const int *rp, const int *ci, const T *val, int m, const int *rp_rest, const int *at, int *rest_ci, T *rest_val, int *rt_cid, T *rt_val)
+__global__ void k_row_tiles_move(const int *rp, const int *ci, const T *val, int m, const int *rp_rest, const int *at, int *rest_ci, T *rest_val, int *rt_cid, T *rt_val,
+                                 const unsigned *src, unsigned *rest_src, unsigned *rt_src /* value map: nullptr = none */)
 {
     const int lane = threadIdx.x & 63, i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= m) return;
@@ -621,6 +671,10 @@ __global__ void k_row_tiles_move(const int *rp, const int *ci, const T *val, int
     int *dc = t >= 0 ? rt_cid + t : rest_ci + rp_rest[i];
     T *dv = t >= 0 ? rt_val + t : rest_val + rp_rest[i];
     for (int j = lane; j < n; j += 64) { dc[j] = ci[a0 + j]; dv[j] = val[a0 + j]; }
+    if (rest_src) {
+        unsigned *ds = t >= 0 ? rt_src + t : rest_src + rp_rest[i];
+        for (int j = lane; j < n; j += 64) ds[j] = map_of(src, a0 + j);
+    }
 }
 int devpack_row_tiles(const Plan &p, DevCsr &panel, const std::vector<int> &rp_rest, const std::vector<int> &at, size_t cnt,
                       std::vector<std::shared_ptr<void>> &keep, DevRowTiles *out)
@@ -632,27 +686,33 @@ int devpack_row_tiles(const Plan &p, DevCsr &panel, const std::vector<int> &rp_r
         keep.emplace_back(*ptr, [](void *q) { (void)hipFree(q); });
         return DASP_OK;
     };
-    void *d_rp = nullptr, *d_at = nullptr, *r_ci = nullptr, *r_val = nullptr, *t_ci = nullptr, *t_val = nullptr;
+    void *d_rp = nullptr, *d_at = nullptr, *r_ci = nullptr, *r_val = nullptr, *t_ci = nullptr, *t_val = nullptr, *r_src = nullptr, *t_src = nullptr;
     if (int rc = dmalloc(((size_t)m + 1) * 4, &d_rp)) return rc;
     if (int rc = dmalloc((size_t)m * 4, &d_at)) return rc;
     if (int rc = dmalloc(n_rest * 4, &r_ci)) return rc;
     if (int rc = dmalloc(n_rest * vb, &r_val)) return rc;
     if (int rc = dmalloc(cnt * 4, &t_ci)) return rc;
     if (int rc = dmalloc(cnt * vb, &t_val)) return rc;
+    if (p.value_map) {      // the value map follows every element to the tiles or to the rest
+        if (int rc = dmalloc(n_rest * 4, &r_src)) return rc;
+        if (int rc = dmalloc(cnt * 4, &t_src)) return rc;
+    }
     HIP_TRYP(hipMemcpy(d_rp, rp_rest.data(), ((size_t)m + 1) * 4, hipMemcpyHostToDevice));
     if (m > 0) {
         HIP_TRYP(hipMemcpy(d_at, at.data(), (size_t)m * 4, hipMemcpyHostToDevice));
         if (p.precision == 64)
             hipLaunchKernelGGL((k_row_tiles_move<double>), dim3(waves_grid(m)), dim3(256), 0, 0, panel.rp, panel.ci, static_cast<const double *>(panel.val), m, static_cast<const int *>(d_rp),
-                               static_cast<const int *>(d_at), static_cast<int *>(r_ci), static_cast<double *>(r_val), static_cast<int *>(t_ci), static_cast<double *>(t_val));
+                               static_cast<const int *>(d_at), static_cast<int *>(r_ci), static_cast<double *>(r_val), static_cast<int *>(t_ci), static_cast<double *>(t_val),
+                               panel.src, static_cast<unsigned *>(r_src), static_cast<unsigned *>(t_src));
         else
             hipLaunchKernelGGL((k_row_tiles_move<_Float16>), dim3(waves_grid(m)), dim3(256), 0, 0, panel.rp, panel.ci, static_cast<const _Float16 *>(panel.val), m, static_cast<const int *>(d_rp),
-                               static_cast<const int *>(d_at), static_cast<int *>(r_ci), static_cast<_Float16 *>(r_val), static_cast<int *>(t_ci), static_cast<_Float16 *>(t_val));
+                               static_cast<const int *>(d_at), static_cast<int *>(r_ci), static_cast<_Float16 *>(r_val), static_cast<int *>(t_ci), static_cast<_Float16 *>(t_val),
+                               panel.src, static_cast<unsigned *>(r_src), static_cast<unsigned *>(t_src));
         HIP_TRYP(hipGetLastError());
         HIP_TRYP(hipDeviceSynchronize());
     }
-    panel = DevCsr{static_cast<const int *>(d_rp), static_cast<const int *>(r_ci), r_val};
-    out->val = t_val; out->cid = static_cast<int *>(t_ci);
+    panel = DevCsr{static_cast<const int *>(d_rp), static_cast<const int *>(r_ci), r_val, static_cast<const uint32_t *>(r_src)};
+    out->val = t_val; out->cid = static_cast<int *>(t_ci); out->map = static_cast<uint32_t *>(t_src);
     return DASP_OK;
 }
 int devpack_place_row_tiles(Plan &q, const DevRowTiles &src)
@@ -661,6 +721,10 @@ int devpack_place_row_tiles(Plan &q, const DevRowTiles &src)
     char *base = static_cast<char *>(q.dev->arena);
     HIP_TRYP(hipMemcpy(base + q.dev->map.rt_val, src.val, q.cnt_rt * (size_t)q.geo.vbytes, hipMemcpyDeviceToDevice));
     HIP_TRYP(hipMemcpy(base + q.dev->map.rt_cid, src.cid, q.cnt_rt * 4, hipMemcpyDeviceToDevice));
+    if (q.value_map && src.map && q.cnt_rt > 0) {
+        HIP_TRYP(hipMalloc(&q.dev->pk_map[4], q.cnt_rt * 4));
+        HIP_TRYP(hipMemcpy(q.dev->pk_map[4], src.map, q.cnt_rt * 4, hipMemcpyDeviceToDevice));
+    }
     return DASP_OK;
 }
 
@@ -692,7 +756,7 @@ int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val)
 {
     if (p.nnz <= 0) return DASP_OK;
     HIP_TRYP(hipMemcpy(ci, d.ci, (size_t)p.nnz * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRYP(hipMemcpy(val, d.val, (size_t)p.nnz * (size_t)p.geo.vbytes, hipMemcpyDeviceToHost));
+    if (val) HIP_TRYP(hipMemcpy(val, d.val, (size_t)p.nnz * (size_t)p.geo.vbytes, hipMemcpyDeviceToHost));
     return DASP_OK;
 }
 int devpack_current_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; } return d; }
@@ -705,6 +769,7 @@ int devpack_all(Plan &p, const DevCsr &d, const PackMeta &m)
     // ... then the kernels above fill those regions straight from the device CSR
     const int rc = p.precision == 64 ? pack_all_typed<double>(p, d, m) : pack_all_typed<_Float16>(p, d, m);
     if (rc == DASP_OK) p.host_dropped = true;       // no host copies of the packed nonzeros exist
+    if (rc == DASP_OK && p.value_map && !p.panel) return value_map_upload(p);      // (a panel's maps go with its parent's: devpack_finish_panels)
     return rc;
 }
 
@@ -737,12 +802,279 @@ int devpack_spin(void *stream, int micros, int channels)
     return DASP_OK;
 }
 
+namespace {
+
+// ---- value refresh (opt.value_map; dasp_plan_update_values).  Every stored value slot of a plan has a map entry: 1 + the caller's CSR index of the
+// nonzero it holds, 0 for a pad (plan.hpp Plan::long_map).  New values with the same pattern are written into the packed arrays by ONE launch over a
+// table of runs -- one run per value array of the plan, its panels, its column-blocked long rows and its two-phase streams.  A workgroup finds its run by
+// a scalar binary search over the runs' first workgroups; a lane owns G consecutive slots per step (f64: 4 values = 32 B of destination and 16 B of map;
+// f16: 8 values = 16 B of destination and 32 B of map), gathers their sources with plain loads (inside a row they are consecutive CSR entries, and a
+// chunk's rows continue in the next chunk: L1 / L2 serve most of them) and stores whole vectors.  The copy moves raw bits: no arithmetic per type.
+struct ValueRun { long long dst_off, map_off, count, blk0; int arena, pad; };
+constexpr int kRefreshMaxArenas = 65;        // the plan + up to 64 column panels
+constexpr int kRefreshThreads = 256, kRefreshSteps = 4;
+struct RefreshBases { char *base[kRefreshMaxArenas]; };
+template <int VB> struct RefreshGeo { static constexpr int G = VB == 8 ? 4 : 8; };
+__host__ __device__ constexpr long long refresh_slots_per_block(int vb) { return (long long)kRefreshThreads * kRefreshSteps * (vb == 8 ? 4 : 8); }
+
+typedef unsigned int vm_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long vm_u64x2 __attribute__((ext_vector_type(2)));
+
+template <class V, bool NT> __device__ __forceinline__ V vm_load(const V *p) { if constexpr (NT) return __builtin_nontemporal_load(p); else return *p; }
+template <class V, bool NT> __device__ __forceinline__ void vm_store(V *p, V v) { if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v; }
+
+template <int VB, bool NT>
+__global__ void __launch_bounds__(kRefreshThreads) dasp_value_refresh_kernel(const ValueRun *__restrict__ runs, int n_runs, const unsigned int *__restrict__ map,
+                                                                           const void *__restrict__ src, RefreshBases bases)
+{
+    using W = std::conditional_t<VB == 8, unsigned long long, unsigned short>;
+    constexpr int G = RefreshGeo<VB>::G;
+    const long long b = blockIdx.x;
+    int lo = 0, hi = n_runs - 1;             // the last run whose first workgroup is <= b (uniform: scalar loads)
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (runs[mid].blk0 <= b) lo = mid; else hi = mid - 1; }
+    const long long count = runs[lo].count, e_blk = (b - runs[lo].blk0) * refresh_slots_per_block(VB);
+    W *dst = reinterpret_cast<W *>(bases.base[runs[lo].arena] + runs[lo].dst_off);
+    const unsigned int *mp = map + runs[lo].map_off;
+    const W *s = static_cast<const W *>(src);
+#pragma unroll
+    for (int step = 0; step < kRefreshSteps; ++step) {
+        const long long e = e_blk + ((long long)step * kRefreshThreads + threadIdx.x) * G;
+        if (e + G <= count) {
+            unsigned int ix[G];
+            const vm_u32x4 m0 = vm_load<vm_u32x4, NT>(reinterpret_cast<const vm_u32x4 *>(mp + e));
+            ix[0] = m0.x; ix[1] = m0.y; ix[2] = m0.z; ix[3] = m0.w;
+            if constexpr (G == 8) {
+                const vm_u32x4 m1 = vm_load<vm_u32x4, NT>(reinterpret_cast<const vm_u32x4 *>(mp + e + 4));
+                ix[4] = m1.x; ix[5] = m1.y; ix[6] = m1.z; ix[7] = m1.w;
+            }
+            W v[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) v[i] = ix[i] ? s[ix[i] - 1u] : (W)0;
+            if constexpr (VB == 8) {
+                vm_store<vm_u64x2, NT>(reinterpret_cast<vm_u64x2 *>(dst + e), vm_u64x2{v[0], v[1]});
+                vm_store<vm_u64x2, NT>(reinterpret_cast<vm_u64x2 *>(dst + e + 2), vm_u64x2{v[2], v[3]});
+            } else {
+                vm_u32x4 o;
+                o.x = (unsigned)v[0] | ((unsigned)v[1] << 16); o.y = (unsigned)v[2] | ((unsigned)v[3] << 16);
+                o.z = (unsigned)v[4] | ((unsigned)v[5] << 16); o.w = (unsigned)v[6] | ((unsigned)v[7] << 16);
+                vm_store<vm_u32x4, NT>(reinterpret_cast<vm_u32x4 *>(dst + e), o);
+            }
+        } else if (e < count) {              // the run's tail: slot by slot, nothing beyond the run
+            for (long long j = e; j < count; ++j) { const unsigned int ix = mp[j]; dst[j] = ix ? s[ix - 1u] : (W)0; }
+        }
+    }
+}
+
+}  // namespace
+
+// the runs of a top-level plan: every (arena, destination offset, host map, slots) -- the same walk at upload and for the host rewrite
+struct HostRun { Plan *owner; size_t dst_off; std::vector<uint32_t> *map; raw_vector<char> *host_val; size_t count; void *dmap; };      // dmap: the packers' device map (device-built plans)
+static void collect_runs(Plan &p, std::vector<HostRun> &out)
+{
+    auto plain = [&](Plan &q) {
+        const ArenaMap *am = q.dev ? &q.dev->map : nullptr;
+        auto add = [&](size_t off, std::vector<uint32_t> &m, raw_vector<char> &v, size_t n, int pk) { if (n) out.push_back({&q, off, &m, &v, n, q.dev ? q.dev->pk_map[pk] : nullptr}); };
+        add(am ? am->long_val : 0, q.long_map, q.long_val, q.cnt_long, 0);
+        add(am ? am->med_val : 0, q.med_map, q.med_val, q.cnt_reg, 1);
+        add(am ? am->irr_val : 0, q.irr_map, q.irr_val, q.cnt_irr, 2);
+        add(am ? am->short_val : 0, q.short_map, q.short_val, q.cnt_short, 3);
+        add(am ? am->rt_val : 0, q.rt_map, q.rt_val, q.cnt_rt, 4);
+    };
+    auto off_in = [&](const void *ptr) -> size_t { return p.dev && ptr ? (size_t)(static_cast<const char *>(ptr) - static_cast<const char *>(p.dev->arena)) : 0; };
+    if (p.two_phase) { if (p.tp.segments) out.push_back({&p, off_in(p.dev ? p.dev->tp.val : nullptr), &p.tp.map, &p.tp.val, p.tp.segments * kTpSeg, nullptr}); }
+    else if (!p.panels.empty()) for (auto &h : p.panels) plain(h->impl);
+    else plain(p);
+    if (p.lcb.n_rows() > 0 && p.lcb.elems) out.push_back({&p, off_in(p.dev ? p.dev->lcb.val : nullptr), &p.lcb.map, &p.lcb.val, p.lcb.elems, nullptr});
+}
+
+static void packer_maps_free(DevicePlan *d)
+{
+    for (void *&q : d->pk_map) { if (q) (void)hipFree(q); q = nullptr; }
+}
+void value_map_free(DevicePlan *d)
+{
+    if (!d) return;
+    if (d->vm_map) (void)hipFree(d->vm_map);
+    if (d->vm_runs) (void)hipFree(d->vm_runs);
+    d->vm_map = d->vm_runs = nullptr; d->vm_n_runs = 0; d->vm_blocks = d->vm_slots = 0; d->vm_arenas.clear(); d->vm_ready = false;
+    packer_maps_free(d);
+}
+
+// the refresh table of an uploaded top-level plan: every run's map (host maps of a host-built plan, the packers' device maps of a device-built one) into one
+// allocation.  Any failure leaves no table behind (vm_ready false: the update entry points refuse the plan instead of doing nothing).
+static int value_map_upload_impl(Plan &p, std::vector<HostRun> &hr)
+{
+    DevicePlan *d = p.dev;
+    std::vector<ValueRun> runs;
+    std::vector<Plan *> arenas;
+    long long entries = 0, blocks = 0, slots = 0;
+    const long long per_block = refresh_slots_per_block(p.geo.vbytes);
+    for (const HostRun &r : hr) {
+        if (r.map->size() != r.count && !r.dmap) { set_error("value map: a map does not match its value array (plan built without value_map?)"); return DASP_ERR_STATE; }
+        if (!r.owner->dev || !r.owner->dev->arena) { set_error("value map: a value array has no device copy"); return DASP_ERR_STATE; }
+        int a = (int)(std::find(arenas.begin(), arenas.end(), r.owner) - arenas.begin());
+        if (a == (int)arenas.size()) arenas.push_back(r.owner);
+        if (a >= kRefreshMaxArenas) { set_error("value map: too many arenas"); return DASP_ERR_STATE; }
+        if (r.dst_off % 32 != 0) { set_error("value map: misaligned value array"); return DASP_ERR_STATE; }
+        ValueRun v{(long long)r.dst_off, entries, (long long)r.count, blocks, a, 0};
+        runs.push_back(v);
+        entries += ((long long)r.count + 7) / 8 * 8;          // every run's map starts on 32 bytes
+        blocks += ((long long)r.count + per_block - 1) / per_block;
+        slots += (long long)r.count;
+    }
+    d->vm_slots = slots;
+    d->vm_arenas = arenas;
+    if (!runs.empty()) {
+        HIP_TRYP(hipMalloc(&d->vm_map, (size_t)entries * 4));
+        HIP_TRYP(hipMemset(d->vm_map, 0, (size_t)entries * 4));
+        for (size_t i = 0; i < runs.size(); ++i) {
+            unsigned int *to = static_cast<unsigned int *>(d->vm_map) + runs[i].map_off;
+            if (hr[i].map->size() == hr[i].count) HIP_TRYP(hipMemcpy(to, hr[i].map->data(), hr[i].count * 4, hipMemcpyHostToDevice));
+            else HIP_TRYP(hipMemcpy(to, hr[i].dmap, hr[i].count * 4, hipMemcpyDeviceToDevice));
+        }
+        HIP_TRYP(hipMalloc(&d->vm_runs, runs.size() * sizeof(ValueRun)));
+        HIP_TRYP(hipMemcpy(d->vm_runs, runs.data(), runs.size() * sizeof(ValueRun), hipMemcpyHostToDevice));
+    }
+    d->vm_n_runs = (int)runs.size(); d->vm_blocks = blocks;
+    return DASP_OK;
+}
+int value_map_upload(Plan &p)
+{
+    DevicePlan *d = p.dev;
+    if (!d || !p.value_map) return DASP_OK;
+    if (d->vm_map) (void)hipFree(d->vm_map);
+    if (d->vm_runs) (void)hipFree(d->vm_runs);
+    d->vm_map = d->vm_runs = nullptr; d->vm_ready = false;
+    std::vector<HostRun> hr;
+    collect_runs(p, hr);
+    const int rc = value_map_upload_impl(p, hr);
+    for (const HostRun &r : hr) if (r.owner->dev) packer_maps_free(r.owner->dev);      // gathered (or given up): the packers' copies go either way
+    if (rc != DASP_OK) { value_map_free(d); return rc; }
+    d->vm_ready = true;
+    return DASP_OK;
+}
+
+static int value_refresh_launch(Plan &p, const void *dval, hipStream_t stream)
+{
+    DevicePlan *d = p.dev;
+    if (d->vm_blocks == 0) return DASP_OK;
+    RefreshBases bases{};
+    for (size_t i = 0; i < d->vm_arenas.size(); ++i) bases.base[i] = static_cast<char *>(d->vm_arenas[i]->dev->arena);      // resolved now: the arena may have moved
+    const dim3 grid((unsigned)d->vm_blocks), block(kRefreshThreads);
+    const auto *runs = static_cast<const ValueRun *>(d->vm_runs);
+    const auto *mp = static_cast<const unsigned int *>(d->vm_map);
+    if (p.precision == 64) {
+        if (d->nt) hipLaunchKernelGGL((dasp_value_refresh_kernel<8, true>), grid, block, 0, stream, runs, d->vm_n_runs, mp, dval, bases);
+        else hipLaunchKernelGGL((dasp_value_refresh_kernel<8, false>), grid, block, 0, stream, runs, d->vm_n_runs, mp, dval, bases);
+    } else {
+        if (d->nt) hipLaunchKernelGGL((dasp_value_refresh_kernel<2, true>), grid, block, 0, stream, runs, d->vm_n_runs, mp, dval, bases);
+        else hipLaunchKernelGGL((dasp_value_refresh_kernel<2, false>), grid, block, 0, stream, runs, d->vm_n_runs, mp, dval, bases);
+    }
+    HIP_TRYP(hipGetLastError());
+    return DASP_OK;
+}
+
+// the host arrays of a plan that still holds them, rewritten from host values through the host maps (threads over slot ranges)
+static void value_refresh_host(Plan &p, const void *val)
+{
+    std::vector<HostRun> hr;
+    collect_runs(p, hr);
+    const size_t vb = (size_t)p.geo.vbytes;
+    const char *s = static_cast<const char *>(val);
+    const int T = resolve_threads(p.opt.host_threads);
+    for (const HostRun &r : hr) {
+        char *dst = r.host_val->data();
+        const uint32_t *mp = r.map->data();
+        const size_t n = r.count, per = std::max<size_t>(1 << 16, (n + (size_t)T - 1) / (size_t)T);
+        std::vector<std::thread> th;
+        auto work = [&](size_t b, size_t e) {
+            for (size_t j = b; j < e; ++j) { if (mp[j]) std::memcpy(dst + j * vb, s + (size_t)(mp[j] - 1) * vb, vb); else std::memset(dst + j * vb, 0, vb); }
+        };
+        for (size_t b = per; b < n; b += per) th.emplace_back(work, b, std::min(n, b + per));
+        work(0, std::min(n, per));
+        for (auto &t : th) t.join();
+    }
+}
+
+// why a plan cannot be refreshed (DASP_OK: it can)
+static int value_map_usable(const Plan &p)
+{
+    if (p.panel) { set_error("a column panel is refreshed through its parent plan (dasp_plan_update_values on the parent)"); return DASP_ERR_ARG; }
+    if (p.loaded) { set_error("a plan loaded from a file carries no value map (plan files do not store one): create the plan with value_map = 1"); return DASP_ERR_STATE; }
+    if (!p.value_map) { set_error("the plan has no value map: create it with dasp_options_t::value_map = 1"); return DASP_ERR_STATE; }
+    return DASP_OK;
+}
+
+}  // namespace dasp
+
+extern "C" {
+
+int dasp_plan_update_values(dasp_plan_t *plan, const void *dVal, void *stream)
+{
+    using namespace dasp;
+    if (!plan || (!dVal && plan->impl.nnz > 0)) { set_error("dasp_plan_update_values: NULL argument"); return DASP_ERR_ARG; }
+    Plan &p = plan->impl;
+    if (int rc = value_map_usable(p)) return rc;
+    if (!p.dev) { set_error("dasp_plan_update_values: the plan is not uploaded (dasp_plan_upload, or dasp_plan_update_values_host for host values)"); return DASP_ERR_STATE; }
+    if (!p.dev->vm_ready) { set_error("dasp_plan_update_values: the plan's value map did not reach the device (its upload failed): upload the plan again"); return DASP_ERR_STATE; }
+    if (!p.host_dropped) if (int rc = dasp_plan_drop_host(plan)) return rc;      // the host copies would go stale
+    return value_refresh_launch(p, dVal, static_cast<hipStream_t>(stream));
+}
+
+int dasp_plan_update_values_host(dasp_plan_t *plan, const void *csrVal)
+{
+    using namespace dasp;
+    if (!plan || (!csrVal && plan->impl.nnz > 0)) { set_error("dasp_plan_update_values_host: NULL argument"); return DASP_ERR_ARG; }
+    Plan &p = plan->impl;
+    if (int rc = value_map_usable(p)) return rc;
+    if (p.dev && !p.dev->vm_ready) { set_error("dasp_plan_update_values_host: the plan's value map did not reach the device (its upload failed): upload the plan again"); return DASP_ERR_STATE; }
+    try {
+        if (!p.host_dropped) value_refresh_host(p, csrVal);
+    } catch (const std::exception &e) { set_error(std::string("dasp_plan_update_values_host: ") + e.what()); return DASP_ERR_NOMEM; }
+    if (p.dev && p.dev->vm_blocks > 0) {
+        const size_t bytes = (size_t)p.nnz * (size_t)p.geo.vbytes;
+        void *stage = nullptr;
+        HIP_TRYP(hipDeviceSynchronize());      // SpMVs of the plan still in flight on any stream (non-blocking ones included) finish before the arrays change
+        HIP_TRYP(hipMalloc(&stage, std::max<size_t>(bytes, 16)));
+        hipError_t e = hipMemcpy(stage, csrVal, bytes, hipMemcpyHostToDevice);
+        int rc = e == hipSuccess ? value_refresh_launch(p, stage, nullptr) : DASP_ERR_HIP;
+        if (e != hipSuccess) set_error(std::string("dasp_plan_update_values_host: staging copy: ") + hipGetErrorString(e));
+        if (rc == DASP_OK && (e = hipStreamSynchronize(nullptr)) != hipSuccess) { set_error(std::string("dasp_plan_update_values_host: ") + hipGetErrorString(e)); rc = DASP_ERR_HIP; }
+        (void)hipFree(stage);
+        return rc;
+    }
+    return DASP_OK;
+}
+
+long long dasp_plan_value_map_slots(const dasp_plan_t *plan)
+{
+    using namespace dasp;
+    if (!plan) return DASP_ERR_ARG;
+    const Plan &p = plan->impl;
+    if (!p.value_map || p.loaded) return 0;
+    if (p.host_dropped) return p.dev ? p.dev->vm_slots : 0;
+    std::vector<HostRun> hr;
+    collect_runs(const_cast<Plan &>(p), hr);
+    long long n = 0;
+    for (const HostRun &r : hr) n += (long long)r.count;
+    return n;
+}
+
+}  // extern "C"
+
+namespace dasp {
+
 // copy a packed array back to the host (tests; serialising a device-built plan)
 int download_array(Plan &p, const char *name, void *dst, size_t bytes)
 {
     if (!p.dev || !p.dev->arena) { set_error("plan not on the device"); return DASP_ERR_STATE; }
     const ArenaMap &mp = p.dev->map;
     const size_t vb = (size_t)p.geo.vbytes;
+    if (std::strcmp(name, "lcb_val") == 0 && p.dev->lcb.val) {      // column-blocked long rows of a column-panel parent or of a two-phase plan
+        if (bytes != p.lcb.elems * vb) { set_error("size mismatch for lcb_val"); return DASP_ERR_ARG; }
+        if (bytes) HIP_TRYP(hipMemcpy(dst, p.dev->lcb.val, bytes, hipMemcpyDeviceToHost));
+        return DASP_OK;
+    }
     if (p.two_phase) {      // the tile streams of a two-phase plan (tp_xs: what phase 1 wrote in the last product)
         const TpDev &q = p.dev->tp;
         const size_t S = p.tp.segments;

@@ -66,7 +66,7 @@ int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const 
     for (size_t q = 0; q < cnt.size(); ++q) { L.ptr[q] = (int)run; run += (cnt[q] + A - 1) / A * A; if (run >= (1ll << 31) - 64) { set_error("long_cb: too many elements"); return DASP_ERR_ARG; } }
     L.ptr[cnt.size()] = (int)run;
     L.elems = (size_t)run;
-    try { L.lcol.resize(L.elems); L.val.resize(L.elems * (size_t)vb); }
+    try { L.lcol.resize(L.elems); L.val.resize(L.elems * (size_t)vb); if (p.value_map) L.map.assign(L.elems, 0u); }
     catch (const std::bad_alloc &) { set_error("out of host memory"); return DASP_ERR_NOMEM; }
     const char *vsrc = static_cast<const char *>(val);
     rows_par([&](int i) {
@@ -77,6 +77,7 @@ int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const 
             const size_t e = (size_t)L.ptr[(size_t)c * (size_t)nL + (size_t)i] + (size_t)cur[(size_t)c]++;
             L.lcol[e] = (uint16_t)(ci[j] - c * cb);
             std::memcpy(L.val.data() + e * (size_t)vb, vsrc + (size_t)j * (size_t)vb, (size_t)vb);
+            if (!L.map.empty()) L.map[e] = map_entry(p, j);
         }
         for (int c = 0; c < n_cb; ++c) {
             const size_t q = (size_t)c * (size_t)nL + (size_t)i;

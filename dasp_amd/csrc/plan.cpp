@@ -270,6 +270,8 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     // opt.sort_columns: rows whose columns do not ascend get their (column, value) pairs sorted by column (stable) -- copies; the caller's arrays stay as they are
     raw_vector<int> ci_sorted;
     raw_vector<T> val_sorted;
+    raw_vector<uint32_t> src_sorted;        // value map: the caller's nonzero (+1) at every position of the sorted CSR
+    struct MapSrcReset { Plan &q; bool on; ~MapSrcReset() { if (on) q.map_src = nullptr; } } map_src_reset{p, mode == kTop};      // map_src never outlives the top-level build
     DevCsr dev_sorted{nullptr, nullptr, nullptr};
     std::vector<std::shared_ptr<void>> sort_keep;
     if (mode == kTop && p.opt.sort_columns > 0 && nnz > 0) {
@@ -285,20 +287,28 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
             });
             if (unsorted) {
                 ci_sorted.resize((size_t)nnz); val_sorted.resize((size_t)nnz);
+                if (p.value_map) src_sorted.resize((size_t)nnz);      // the map follows each value to its new position
                 parallel_for(m, threads, 1 << 12, [&](long long b, long long e) {
-                    std::vector<std::pair<int, T>> row;
+                    struct Entry { int c; T v; uint32_t s; };
+                    std::vector<Entry> row;
                     for (long long i = b; i < e; ++i) {
                         const int a0 = rp[i], a1 = rp[i + 1];
                         bool ok = true;
                         for (int j = a0 + 1; j < a1; ++j) if (ci[j] < ci[j - 1]) { ok = false; break; }
-                        if (ok) { for (int j = a0; j < a1; ++j) { ci_sorted[(size_t)j] = ci[j]; val_sorted[(size_t)j] = val[j]; } continue; }
+                        if (ok) {
+                            for (int j = a0; j < a1; ++j) { ci_sorted[(size_t)j] = ci[j]; val_sorted[(size_t)j] = val[j]; }
+                            if (p.value_map) for (int j = a0; j < a1; ++j) src_sorted[(size_t)j] = (uint32_t)j + 1u;
+                            continue;
+                        }
                         row.resize((size_t)(a1 - a0));
-                        for (int j = a0; j < a1; ++j) row[(size_t)(j - a0)] = {ci[j], val[j]};
-                        std::stable_sort(row.begin(), row.end(), [](const std::pair<int, T> &x, const std::pair<int, T> &y) { return x.first < y.first; });
-                        for (int j = a0; j < a1; ++j) { ci_sorted[(size_t)j] = row[(size_t)(j - a0)].first; val_sorted[(size_t)j] = row[(size_t)(j - a0)].second; }
+                        for (int j = a0; j < a1; ++j) row[(size_t)(j - a0)] = {ci[j], val[j], (uint32_t)j + 1u};
+                        std::stable_sort(row.begin(), row.end(), [](const Entry &x, const Entry &y) { return x.c < y.c; });
+                        for (int j = a0; j < a1; ++j) { const Entry &q = row[(size_t)(j - a0)]; ci_sorted[(size_t)j] = q.c; val_sorted[(size_t)j] = q.v; }
+                        if (p.value_map) for (int j = a0; j < a1; ++j) src_sorted[(size_t)j] = row[(size_t)(j - a0)].s;
                     }
                 });
                 ci = ci_sorted.data(); val = val_sorted.data();
+                if (p.value_map) p.map_src = src_sorted.data();
             }
         }
         lap("sort columns");
@@ -341,8 +351,15 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
             else {
                 raw_vector<int> hci((size_t)nnz);
                 raw_vector<T> hval((size_t)nnz);
+                raw_vector<uint32_t> hsrc;
                 if (int rc = devpack_fetch_csr(p, *dev, hci.data(), hval.data())) return rc;
+                if (p.value_map && dev->src) {      // a column-sorted device CSR: its map entries travel too (else the host's own index + 1 is the map)
+                    hsrc.resize((size_t)nnz);
+                    if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(hsrc.data()), nullptr)) return rc;
+                    p.map_src = hsrc.data();
+                }
                 rc2 = hybrid_then_tp(hci.data(), hval.data());
+                p.map_src = nullptr;      // (hsrc ends here)
                 lap("two-phase streams (device CSR fetched)");
                 if (rc2 == DASP_OK) return devpack_finish_panels(p);       // a device-built plan comes back uploaded
                 if (rc2 != kTpDeclined) return rc2;
@@ -938,6 +955,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         if (pack) {
         p.long_val.resize((size_t)total * sizeof(T));          // not zero-filled: rows + their pads are written below
         p.long_cid.resize((size_t)total);
+        if (p.value_map) p.long_map.assign((size_t)total, 0u);      // pads stay 0
         }
         p.piece_ptr.clear(); p.piece_dst.clear(); p.multi_ptr.assign(1, 0); p.multi_dst.clear();
         int n_partial = 0;
@@ -961,6 +979,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
                 const long long real_end = std::min(s1, start[i] + len);
                 const long long src = (long long)rp[r] - start[i];
                 for (long long j = s0; j < real_end; ++j) { lv[j] = val[src + j]; p.long_cid[(size_t)j] = remap(ci[src + j]); }
+                if (p.value_map) for (long long j = s0; j < real_end; ++j) p.long_map[(size_t)j] = map_entry(p, src + j);
                 for (long long j = std::max(s0, real_end); j < s1; ++j) { lv[j] = (T)0; p.long_cid[(size_t)j] = -1; }   // pad to kLongAlign
             }
         });
@@ -1134,6 +1153,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     p.med_cid8.resize(p.cnt_reg8);
     p.irr_val.resize((size_t)nnz_irreg * sizeof(T));           // fully covered by the rows' tails
     p.irr_cid.resize((size_t)nnz_irreg);
+    if (p.value_map) { p.med_map.assign((size_t)n_reg, 0u); p.irr_map.assign((size_t)nnz_irreg, 0u); }      // pads stay 0
     }
     if (pack) {
         T *mv = reinterpret_cast<T *>(p.med_val.data());
@@ -1191,6 +1211,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
                         const int lane = f16 ? (kk / 4) * kMedRows + rr : kk * kMedRows + rr, j = f16 ? kk % 4 : 0;
                         const size_t at = base + med_elem_index(npair, q, lane, j, VPL, CH);
                         mv[at] = val[a0 + i];
+                        if (p.value_map) p.med_map[at] = map_entry(p, a0 + i);
                         const int col = remap(ci[a0 + i]);
                         if (!p.cid16) p.med_cid[at] = col;
                         else if (q < n8) p.med_cid8[e8 + med_cid8_index(q, lane, CH, oneshot)] = (uint8_t)(col - lo_of[c]);
@@ -1199,6 +1220,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
                     const int t0 = p.irr_ptr[r], tl = p.irr_ptr[r + 1] - t0;
                     for (int j = 0; j < tl; ++j) {   // the LAST tl entries of the row (dasp_f64.h:1094-1106)
                         iv[t0 + j] = val[a0 + len - tl + j];
+                        if (p.value_map) p.irr_map[(size_t)(t0 + j)] = map_entry(p, a0 + len - tl + j);
                         p.irr_cid[t0 + j] = remap(ci[a0 + len - tl + j]);
                     }
                 }
@@ -1253,6 +1275,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         if (pack) {
         p.short_val.resize((size_t)off * sizeof(T));           // not zero-filled: only a slab's last tile has pads
         p.short_cid.resize((size_t)off);
+        if (p.value_map) p.short_map.assign((size_t)off, 0u);      // pads stay 0
         T *sv = reinterpret_cast<T *>(p.short_val.data());
         for (int g = 0; g < kNumShortGroups; ++g) {
             const ShortGroup &G = p.grp[g];
@@ -1273,6 +1296,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
                     for (int k = 0; k < G.len; ++k) {
                         const size_t at = (size_t)G.elem_off + short_elem_index(G.seg != 0, G.len, SR, t, k);
                         sv[at] = val[a0 + k];
+                        if (p.value_map) p.short_map[at] = map_entry(p, a0 + k);
                         p.short_cid[at] = remap(ci[a0 + k]);
                     }
                 }
@@ -1482,6 +1506,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     std::vector<std::vector<int>> rpP((size_t)P);
     std::vector<raw_vector<int>> ciP((size_t)P);
     std::vector<raw_vector<T>> valP((size_t)P);
+    std::vector<raw_vector<uint32_t>> srcP((size_t)P);   // value map: the caller's nonzero (+1) at every position of panel k's sub-CSR
     std::vector<DevCsr> devP;                          // device CSR: the same split by two kernels (devpack.hip), sub-matrices stay on the GPU
     std::vector<std::shared_ptr<void>> dev_keep;
     std::vector<DevRowTiles> rt_dev((size_t)P);        // device path: the tiles' elements, moved into the panel plan's arena once it exists
@@ -1494,11 +1519,17 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     std::vector<unsigned char> in_lcb;
     raw_vector<int> lcb_ci;
     raw_vector<T> lcb_val;
+    raw_vector<uint32_t> lcb_src;
     p.lcb = LongCB{};
     if (decide_long_cb(p, rp, P, in_lcb) > 0) {
         if (dev) {      // their cut by column block runs on the host for now: fetch the nonzeros once, then the host split below
             lcb_ci.resize((size_t)p.nnz); lcb_val.resize((size_t)p.nnz);
             if (int rc = devpack_fetch_csr(p, *dev, lcb_ci.data(), lcb_val.data())) return rc;
+            if (p.value_map && dev->src) {      // (see the two-phase fetch in build_impl)
+                lcb_src.resize((size_t)p.nnz);
+                if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(lcb_src.data()), nullptr)) return rc;
+                p.map_src = lcb_src.data();
+            }
             ci = lcb_ci.data(); val = lcb_val.data(); dev = nullptr;
         }
         const int rc_lcb = build_long_cb(p, rp, ci, val, in_lcb, natural ? nullptr : slot_of_row.data());
@@ -1512,7 +1543,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     int rt_max = p.opt.row_tile_max == 0 ? (p.precision == 16 ? kRowTileAuto : kRowTileAuto64) : std::max(0, p.opt.row_tile_max);
     if (rt_max > kRowTileMax) { set_error("row_tile_max must be <= 32"); return DASP_ERR_ARG; }
     if (p.opt.row_tile_max == 0 && ab_knobs().row_tile_max >= 0) rt_max = std::min(kRowTileMax, ab_knobs().row_tile_max);      // A/B knob: only over "auto", never over a caller's choice
-    struct RowTiles { std::vector<int> ptr; std::vector<uint16_t> start; std::vector<uint64_t> mask; raw_vector<char> val; raw_vector<int> cid; std::vector<int> at; size_t cnt = 0; };
+    struct RowTiles { std::vector<int> ptr; std::vector<uint16_t> start; std::vector<uint64_t> mask; raw_vector<char> val; raw_vector<int> cid; std::vector<int> at; size_t cnt = 0; std::vector<uint32_t> map; };
     std::vector<RowTiles> rt((size_t)P);
     // from a panel's row LENGTHS in len[1 .. m] (len[i + 1] = row i): the tiles' tables; the rows taken get length 0 in len
     auto cut_row_tiles = [&](RowTiles &R, int *len) {
@@ -1566,6 +1597,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     });
     const size_t vb = (size_t)p.geo.vbytes;
     for (int k = 0; k < P; ++k) { ciP[k].resize((size_t)rpP[k][m]); valP[k].resize((size_t)rpP[k][m]); rt[(size_t)k].cid.resize(rt[(size_t)k].cnt); rt[(size_t)k].val.resize(rt[(size_t)k].cnt * vb); }
+    if (p.value_map) for (int k = 0; k < P; ++k) { srcP[k].resize((size_t)rpP[k][m]); rt[(size_t)k].map.assign(rt[(size_t)k].cnt, 0u); }
     parallel_for(m, threads, 1 << 12, [&](long long b, long long e) {
         std::vector<int> cur((size_t)P);
         std::vector<char> tiled((size_t)P);
@@ -1576,6 +1608,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
                 const int c = remap(ci[j]), k = panel_of(c), at = cur[k]++;
                 if (tiled[k]) { rt[(size_t)k].cid[(size_t)at] = c; reinterpret_cast<T *>(rt[(size_t)k].val.data())[at] = val[j]; }
                 else { ciP[k][at] = c; valP[k][at] = val[j]; }
+                if (p.value_map) (tiled[k] ? rt[(size_t)k].map[(size_t)at] : srcP[k][(size_t)at]) = map_entry(p, j);
             }
         }
     });
@@ -1612,9 +1645,10 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
                     q.opt.col_panels = 1; q.opt.host_threads = each;
                     if (q.opt.stream_policy == 0) q.opt.stream_policy = streams ? 2 : 1;   // the policy follows the whole matrix, not one panel
                     q.dst_map = slot_of_row; q.panel = true;
+                    q.value_map = p.value_map; q.map_src = p.value_map && !dev ? srcP[k].data() : nullptr;      // (device panels: DevCsr::src)
                     if (R.cnt > 0) {      // (a panel none of whose rows is short enough keeps no tiles at all)
                         q.rt_max = rt_max; q.cnt_rt = R.cnt;
-                        q.rt_ptr.swap(R.ptr); q.rt_start.swap(R.start); q.rt_mask.swap(R.mask); q.rt_val.swap(R.val); q.rt_cid.swap(R.cid);
+                        q.rt_ptr.swap(R.ptr); q.rt_start.swap(R.start); q.rt_mask.swap(R.mask); q.rt_val.swap(R.val); q.rt_cid.swap(R.cid); q.rt_map.swap(R.map);
                         q.opt.x_window = -1; q.opt.cid8 = -1;      // the tiles ride in the non-windowed kernel without one-byte ids (dasp_spmv_rt_kernel)
                     }
                     // f16 only: 2-byte stores are where the partial lines hurt (ljournal-2008-uniform 0.590 -> 0.559 ms, ljournal-2008 0.506 -> 0.503; powerlaw_1M f64 0.651 -> 0.654)
@@ -1623,14 +1657,14 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
                     catch (const std::bad_alloc &) { rcs[k] = DASP_ERR_NOMEM; set_error("out of host memory"); }
                     if (rcs[k] == DASP_OK && dev && q.cnt_rt > 0) rcs[k] = devpack_place_row_tiles(q, rt_dev[(size_t)k]);
                     if (rcs[k] != DASP_OK) { errs[k] = last_error_cstr(); continue; }
-                    q.opt.host_threads = p.opt.host_threads; q.scan_order = nullptr;
+                    q.opt.host_threads = p.opt.host_threads; q.scan_order = nullptr; q.map_src = nullptr;
                     {   // the tiles in the panel's counters
                         dasp_stats_t &t = q.stats;
                         t.row_tile_max = q.rt_max; t.n_row_tiles = (int)q.rt_mask.size(); t.row_tile_nnz = (long long)q.cnt_rt;
                         t.n_workgroups += ceil_div(t.n_row_tiles, kWavesPerWG);
                         t.data_X += (long long)q.cnt_rt * (p.geo.vbytes + 4) + (long long)t.n_row_tiles * (4 + 2 * kRowTile + 8);
                     }
-                    std::vector<int>().swap(rpP[k]); raw_vector<int>().swap(ciP[k]); raw_vector<T>().swap(valP[k]);
+                    std::vector<int>().swap(rpP[k]); raw_vector<int>().swap(ciP[k]); raw_vector<T>().swap(valP[k]); raw_vector<uint32_t>().swap(srcP[k]);
                     built[k] = std::move(h);
                 }
             };
@@ -1690,6 +1724,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
 int build_plan(Plan &p, const int *rp, const int *ci, const void *val, const DevCsr *dev)
 {
     p.geo = geometry_for(p.precision);
+    p.value_map = p.opt.value_map == 1;
     if (p.precision == 64) return build_impl<double>(p, rp, ci, static_cast<const double *>(val), dev);
     return build_impl<_Float16>(p, rp, ci, static_cast<const _Float16 *>(val), dev);
 }

@@ -197,6 +197,7 @@ struct TwoPhase {
     raw_vector<uint16_t> lcol;        // [segments * kTpSeg] CB-major: column - c * cb
     raw_vector<uint16_t> lrow;        // [segments * kTpSeg] RB-major: output position - rb_row0[r]
     raw_vector<char> val;             // [segments * kTpSeg * vbytes] RB-major
+    std::vector<uint32_t> map;        // [segments * kTpSeg] value map of val (opt.value_map; Plan::long_map); empty without one
     size_t segments = 0;
     int n_rb() const { return rb_row0.empty() ? 0 : (int)rb_row0.size() - 1; }
     int n_units() const { return (int)(unit.size() / 3); }
@@ -226,6 +227,7 @@ struct LongCB {
     std::vector<int> unit;            // [n_units * 3] column block, first piece, end piece
     raw_vector<uint16_t> lcol;        // [elems] column - c * cb (pads: kLcbPadCol)
     raw_vector<char> val;             // [elems * vbytes]
+    std::vector<uint32_t> map;        // [elems] value map of val (opt.value_map); empty without one
     size_t elems = 0;
     int n_rows() const { return (int)row_dst.size(); }
     int n_units() const { return (int)(unit.size() / 3); }
@@ -333,6 +335,15 @@ struct Plan {
     bool two_phase = false;
     TwoPhase tp;
 
+    // value map (opt.value_map = 1): for every stored slot of a value array, 1 + the index of the nonzero of the CALLER's CSR it holds (through
+    // the column sort and the panel split), 0 for a pad.  Same element counts as the value arrays; every nonzero appears exactly once over all
+    // maps of a plan (its panels, lcb and tp included).  Written beside every value the packers write; empty without a map and after drop_host.
+    bool value_map = false;
+    std::vector<uint32_t> long_map, med_map, irr_map, short_map, rt_map;
+    // (building only) map entry of nonzero j of the CSR handed to the packers: map_src[j], or j + 1 when null (the caller's own CSR)
+    const uint32_t *map_src = nullptr;
+    bool loaded = false;               // from dasp_plan_load (plan files carry no map)
+
     bool host_dropped = false;
     DevicePlan *dev = nullptr;
 
@@ -341,7 +352,7 @@ struct Plan {
 
 // ---- device-side packing (dasp_plan_create_device): the CSR stays on the GPU; the host keeps doing the O(rows) decisions
 // from the row pointer alone and hands the O(nnz) work to the kernels in devpack.hip through these hooks.
-struct DevCsr { const int *rp, *ci; const void *val; };      // device pointers
+struct DevCsr { const int *rp, *ci; const void *val; const uint32_t *src = nullptr; };      // device pointers; src (value map): map entry of each nonzero, nullptr = index + 1
 struct PackMeta {                                             // what the device packers need, in packing order
     const std::vector<int> *ridL = nullptr; const std::vector<long long> *startL = nullptr;
     const raw_vector<int> *ridM = nullptr, *lenM = nullptr;      // (not zero-filled on construction: 33 MB each for 8 M rows)
@@ -358,7 +369,7 @@ int devpack_chunk_spans(const Plan &p, const DevCsr &d, const raw_vector<int> &r
                         const std::vector<int> &nchunks, int *k16, unsigned long long *narrow_mask);      // narrow_mask: nullptr or [blocks] (plan.cpp)
 int devpack_all(Plan &p, const DevCsr &d, const PackMeta &m);
 int devpack_finish_panels(Plan &p);
-int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val);      // column ids and values of a device CSR -> host arrays of nnz elements
+int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val);      // column ids and values of a device CSR -> host arrays of nnz elements (val nullptr: the ids only)
 // the calling thread's HIP device / make `device` the calling thread's (panel workers of a device-built plan)
 int devpack_current_device();
 void devpack_use_device(int device);
@@ -371,7 +382,7 @@ int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &
 // row tiles of a device-built column panel (plan.cpp build_panels): `panel` = the split's sub-matrix, rp_rest = the row pointer of the rows that
 // stay with the panel's plan (host), at[row] = first element of a tiled row in the tiles' arrays (-1: not tiled), cnt = their elements.
 // On return `panel` is the sub-matrix of the remaining rows only and `out` holds the tiles' elements (device, owned by `keep`).
-struct DevRowTiles { void *val = nullptr; int *cid = nullptr; };
+struct DevRowTiles { void *val = nullptr; int *cid = nullptr; uint32_t *map = nullptr; };      // map: value map entries of the tiles' elements (value_map plans)
 int devpack_row_tiles(const Plan &p, DevCsr &panel, const std::vector<int> &rp_rest, const std::vector<int> &at, size_t cnt,
                       std::vector<std::shared_ptr<void>> &keep, DevRowTiles *out);
 // ... and their copy into the uploaded panel plan's arena (ArenaMap::rt_val / rt_cid)
@@ -401,6 +412,8 @@ inline int win_fold_tiles(int n_windows, int n_short_tiles)
 }
 constexpr int kTpDeclined = 1;          // build_two_phase under the automatic rule: the padded streams would pass 3 x the nonzeros (or the tile table 64 M entries) -- not an error
 int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, const unsigned char *skip = nullptr);
+// value map entry of nonzero j of the CSR the packers read (Plan::map_src)
+inline uint32_t map_entry(const Plan &p, long long j) { return p.map_src ? p.map_src[j] : (uint32_t)(j + 1); }
 bool validate_two_phase(const Plan &p, std::string &why);
 
 // column-blocked long rows (longcb.cpp): which rows (in_lcb[row] = 1) a column-panel plan of P panels hands to them (0 rows: none), the packer, the checks

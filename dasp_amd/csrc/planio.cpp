@@ -344,6 +344,7 @@ static bool read_plan(Reader &r, Plan &p, int depth, std::string &r_why)
     p.cnt_reg8 = p.med_cid8.size();
     p.cnt_rt = p.rt_cid.size();
     p.host_dropped = false;
+    p.loaded = true;      // (a plan file carries no value map: dasp_plan_update_values refuses it)
     p.panel = depth > 0;
     if (!validate_plan(p, np, depth > 0, r_why)) return false;
     p.opt.col_panels = np > 0 ? np : 1;

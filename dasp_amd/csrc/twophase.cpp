@@ -134,6 +134,7 @@ int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, cons
     for (int b = 0; b <= n_rb; ++b) t.rb_seg0[(size_t)b] = (int)off2[std::min((size_t)b * (size_t)n_cb, cnt.size())];
     try {
         t.lcol.resize(S * kTpSeg); t.lrow.resize(S * kTpSeg); t.val.resize(S * kTpSeg * (size_t)vb); t.dst.resize(S);
+        if (p.value_map) t.map.assign(S * kTpSeg, 0u);      // pads stay 0
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return DASP_ERR_NOMEM; }
     const char *vsrc = static_cast<const char *>(val);
     // ---- fill, one row block at a time: a tile's nonzeros in CSR order (rows in output order), then its pads
@@ -148,6 +149,7 @@ int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, cons
                 const size_t e2 = (size_t)off2[base + (size_t)c] * kTpSeg + (size_t)k, e1 = (size_t)off1[base + (size_t)c] * kTpSeg + (size_t)k;
                 t.lrow[e2] = (uint16_t)(pos - pos0);
                 std::memcpy(t.val.data() + e2 * (size_t)vb, vsrc + (size_t)j * (size_t)vb, (size_t)vb);
+                if (!t.map.empty()) t.map[e2] = map_entry(p, j);
                 t.lcol[e1] = (uint16_t)(ci[j] - c * cb);
             }
         }

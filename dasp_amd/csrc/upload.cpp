@@ -30,6 +30,7 @@ namespace dasp {
 Plan::~Plan()
 {
     if (dev) {
+        value_map_free(dev);
         if (dev->arena) (void)hipFree(dev->arena);
         if (dev->dargs) (void)hipFree(dev->dargs);
         std::free(dev->args_sent);
@@ -110,7 +111,7 @@ static int upload_plan_impl(Plan &p)
     if (int rc = require_device()) return rc;
     if (p.host_dropped && p.dev) return DASP_OK;   // already on the device (packed there, or host copies released)
     if (p.host_dropped) { set_error("host arrays were dropped"); return DASP_ERR_STATE; }
-    if (p.dev) { if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
+    if (p.dev) { value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
     auto *d = new DevicePlan();
     p.dev = d;
     HIP_TRY(hipGetDevice(&d->device));
@@ -484,6 +485,7 @@ int upload_plan(Plan &p)
 {
     const bool fresh = !(p.host_dropped && p.dev);
     if (int rc = upload_plan_impl(p)) return rc;
+    if (fresh && p.value_map && !p.panel) if (int rc = value_map_upload(p)) return rc;      // (a panel's maps go with its parent's)
     int trials = 1;
     if (const char *e = std::getenv("DASP_PLACEMENT_TRIALS")) trials = std::max(1, std::min(8, std::atoi(e)));
     return fresh && trials > 1 ? tune_placement(p, trials, nullptr, nullptr, nullptr, nullptr) : DASP_OK;

@@ -206,6 +206,13 @@ typedef struct dasp_options {
      * streamed, nothing gathers from global memory.  0 = auto (when those rows hold >= a quarter of the nonzeros of a plan that uses column panels), 1 = force
      * (every row of >= block_longest nonzeros), -1 = off.  order_rid and the classifier counters are unchanged; a long row's products are added per piece. */
     int long_cb;
+    /* value map (no reference counterpart): 1 = record, for every stored value slot of the plan, the CSR nonzero it came from, so that
+     * dasp_plan_update_values can rewrite the packed values from a new CSR value array with the same pattern, without re-planning.
+     * 0 = no map (default; every other value is DASP_ERR_ARG).  Packed arrays, order_rid, the automatic choices and the stats are those of the
+     * same plan without a map.  Cost: 4 bytes per stored slot on the host while the host arrays live, and 4 bytes per slot in a device allocation
+     * of its own once uploaded (HV15R f64: ~1.1 GB).  Plans from dasp_plan_create and dasp_plan_create_device (whose packers write the map on
+     * the GPU) alike; the multi-GPU layer never keeps one. */
+    int value_map;
 } dasp_options_t;
 
 void dasp_options_default(dasp_options_t *opt);
@@ -312,6 +319,22 @@ long long dasp_plan_host_array(const dasp_plan_t *plan, const char *name, const 
 int dasp_plan_upload(dasp_plan_t *plan);
 /* release the host copies of the packed arrays once uploaded (order_rid and stats stay) */
 int dasp_plan_drop_host(dasp_plan_t *plan);
+
+/* new values, same pattern (plans built with dasp_options_t::value_map = 1; no reference counterpart -- the reference packs on every
+ * call).  dVal: nnzA device values of the plan's precision in the CSR order the plan was created from (after symmetric expansion, before
+ * any sort_columns reordering).  Rewrites every packed value array of the uploaded plan (panels, column-blocked long rows and two-phase
+ * streams included) with one kernel launch, asynchronous on `stream` and ordered with the SpMVs on it; only kernel launches, so safe
+ * inside a stream capture.  An update must not overlap an SpMV of the same plan on another stream.  Host copies of the packed arrays
+ * still held are dropped first (as dasp_plan_drop_host), so that they cannot go stale.
+ * DASP_ERR_STATE: the plan has no map, was loaded from a file (files carry no map), is not uploaded or its map's upload failed; DASP_ERR_ARG: NULL arguments or a
+ * borrowed panel handle (panels are refreshed through their parent). */
+int dasp_plan_update_values(dasp_plan_t *plan, const void *dVal, void *stream);
+/* the same from host values: the host arrays (if held) are rewritten on the CPU; an uploaded plan's device arrays through a staging copy
+ * and the same kernel.  On an uploaded plan it synchronises the device first (SpMVs still in flight on any stream finish before the arrays
+ * change) and again before it returns.  A plan that was never uploaded can so be refreshed and then saved. */
+int dasp_plan_update_values_host(dasp_plan_t *plan, const void *csrVal);
+/* mapped value slots over all value arrays of the plan (panels included); 0 without a map */
+long long dasp_plan_value_map_slots(const dasp_plan_t *plan);
 
 /* switch the cache policy of an uploaded plan (values as dasp_options_t::stream_policy); no re-upload */
 int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);
