@@ -253,6 +253,14 @@ class Plan:
         _lib.check(_lib.lib().dasp_plan_update_values(self._h, C.c_void_p(d_val), C.c_void_p(stream)))
 
     @property
+    def csr_fetch_bytes(self):
+        """Bytes of the caller's nnz-sized device arrays that `from_device` copied to the host while it built this plan (0: everything was packed on the GPU)."""
+        n = int(_lib.lib().dasp_plan_csr_fetch_bytes(self._h))
+        if n < 0:
+            _lib.check(n)
+        return n
+
+    @property
     def value_map_slots(self):
         """Mapped value slots over all value arrays (panels included); 0 without a map."""
         n = int(_lib.lib().dasp_plan_value_map_slots(self._h))

@@ -309,6 +309,8 @@ static long long host_array_impl(const dasp_plan_t *plan, const char *name, cons
     return DASP_ERR_ARG;
 }
 
+long long dasp_plan_csr_fetch_bytes(const dasp_plan_t *plan) { return plan ? plan->impl.csr_fetch_bytes : (long long)DASP_ERR_ARG; }
+
 int dasp_plan_upload(dasp_plan_t *plan)
 {
     if (!plan) return DASP_ERR_ARG;

@@ -117,7 +117,7 @@ struct DevicePlan {
     // index i writes into; its base is read at every launch, so that an arena moved by the placement trials is still found.
     void *vm_map = nullptr, *vm_runs = nullptr;
     bool vm_ready = false;          // the table is complete (a failed map upload leaves it false: dasp_plan_update_values refuses the plan)
-    void *pk_map[5] = {};           // device-built plans: the packers' maps of long / med / irr / short / rt values, until value_map_upload gathers them
+    void *pk_map[7] = {};           // device-built plans: the packers' maps of long / med / irr / short / rt / two-phase / column-blocked values, until value_map_upload gathers them
     int vm_n_runs = 0;
     long long vm_blocks = 0, vm_slots = 0;
     std::vector<Plan *> vm_arenas;

@@ -11,6 +11,9 @@
 #include <thread>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -471,11 +474,12 @@ __device__ __forceinline__ int panel_of_dev(const int *bnd, int P, int c)
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (bnd[mid] <= c) lo = mid; else hi = mid; }
     return lo;
 }
-__global__ void k_panel_count(const int *rp, const int *ci, int m, RemapDev remap, const int *bnd, int P, int *cnt /* [P][m + 1] */)
+// mask (nullptr: none): mask[row] != 0 = the row is empty in every panel (the hub rows of a plan whose Plan::lcb holds them; plan.cpp's host split skips them too)
+__global__ void k_panel_count(const int *rp, const int *ci, int m, RemapDev remap, const int *bnd, int P, int *cnt /* [P][m + 1] */, const unsigned char *mask)
 {
     const int lane = threadIdx.x & 63, i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= m) return;
-    const int a0 = rp[i], a1 = rp[i + 1];
+    const int a0 = rp[i], a1 = mask && mask[i] ? a0 : rp[i + 1];
     int mine = 0;
     for (int j0 = a0; j0 < a1; j0 += 64) {
         const int j = j0 + lane;
@@ -489,11 +493,12 @@ __global__ void k_panel_count(const int *rp, const int *ci, int m, RemapDev rema
 }
 template <class T>
 __global__ void k_panel_scatter(const int *rp, const int *ci, const T *val, int m, RemapDev remap, const int *bnd, int P,
-                                const int *rpP /* [P][m + 1], scanned */, int *const *ciP, T *const *valP, const unsigned *src, unsigned *const *srcP /* nullptr: no map */)
+                                const int *rpP /* [P][m + 1], scanned */, int *const *ciP, T *const *valP, const unsigned *src, unsigned *const *srcP /* nullptr: no map */,
+                                const unsigned char *mask)
 {
     const int lane = threadIdx.x & 63, i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (i >= m) return;
-    const int a0 = rp[i], a1 = rp[i + 1];
+    const int a0 = rp[i], a1 = mask && mask[i] ? a0 : rp[i + 1];
     int cursor = lane < P ? rpP[(size_t)lane * ((size_t)m + 1) + (size_t)i] : 0;
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     for (int j0 = a0; j0 < a1; j0 += 64) {
@@ -517,6 +522,11 @@ __global__ void k_panel_scatter(const int *rp, const int *ci, const T *val, int 
 int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
                         std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep)
 {
+    return devpack_panel_split_masked(p, d, bnd, P, rpP_host, out, keep, nullptr);
+}
+int devpack_panel_split_masked(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
+                               std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep, const unsigned char *mask)
+{
     const int m = p.m;
     const size_t vb = (size_t)p.geo.vbytes, row = (size_t)m + 1;
     auto dmalloc = [&](size_t bytes, void **ptr) -> int {
@@ -526,10 +536,15 @@ int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &
     };
     RemapHolder rm; if (int rc = rm.init(p)) return rc;
     DevVec<int> dbnd; if (int rc = dbnd.init(bnd)) return rc;
+    void *dmask = nullptr;
+    if (mask && m > 0) {
+        if (int rc = dmalloc((size_t)m, &dmask)) return rc;
+        HIP_TRYP(hipMemcpy(dmask, mask, (size_t)m, hipMemcpyHostToDevice));
+    }
     void *cnt = nullptr;
     if (int rc = dmalloc(row * (size_t)P * sizeof(int), &cnt)) return rc;
     HIP_TRYP(hipMemset(cnt, 0, row * (size_t)P * sizeof(int)));
-    if (m > 0) hipLaunchKernelGGL(k_panel_count, dim3(waves_grid(m)), dim3(256), 0, 0, d.rp, d.ci, m, rm.r, dbnd.d, P, static_cast<int *>(cnt));
+    if (m > 0) hipLaunchKernelGGL(k_panel_count, dim3(waves_grid(m)), dim3(256), 0, 0, d.rp, d.ci, m, rm.r, dbnd.d, P, static_cast<int *>(cnt), static_cast<const unsigned char *>(dmask));
     HIP_TRYP(hipGetLastError());
     // the panels' row pointers: an inclusive scan of each panel's counts in place on the device (element 0 of a panel is 0), then every
     // panel's pointer comes to the host in a thread of its own -- the host stages of the panel builds read it.  (First version: all counts
@@ -585,10 +600,10 @@ int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &
     if (m > 0) {
         if (p.precision == 64)
             hipLaunchKernelGGL((k_panel_scatter<double>), dim3(waves_grid(m)), dim3(256), 0, 0, d.rp, d.ci, static_cast<const double *>(d.val), m, rm.r, dbnd.d, P,
-                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<double *const *>(pv), d.src, srcP);
+                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<double *const *>(pv), d.src, srcP, static_cast<const unsigned char *>(dmask));
         else
             hipLaunchKernelGGL((k_panel_scatter<_Float16>), dim3(waves_grid(m)), dim3(256), 0, 0, d.rp, d.ci, static_cast<const _Float16 *>(d.val), m, rm.r, dbnd.d, P,
-                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<_Float16 *const *>(pv), d.src, srcP);
+                               static_cast<const int *>(cnt), static_cast<int *const *>(pc), static_cast<_Float16 *const *>(pv), d.src, srcP, static_cast<const unsigned char *>(dmask));
     }
     HIP_TRYP(hipGetLastError());
     HIP_TRYP(hipDeviceSynchronize());
@@ -749,6 +764,319 @@ int devpack_gather_columns(const Plan &p, const DevCsr &d, const std::vector<lon
     return DASP_OK;
 }
 
+// ---- the two-phase streams (plan.hpp struct TwoPhase) and the column-blocked long rows (struct LongCB) of a device CSR (r8).  The host packers (twophase.cpp,
+// longcb.cpp) give a nonzero the next free place of its bin -- a (row block, column block) tile, a (column block, hub row) piece -- while they walk the rows in
+// output order and every row in CSR order.  That rank is a serial notion; here it comes out of a STABLE LSD radix sort (hipcub) of (key, CSR index) pairs taken in
+// plain CSR order: key = bin << 13 | the row's position inside its row block for the tiles, the bin alone for the pieces (a piece belongs to one row).  Equal keys keep
+// their CSR order, so the rank of a nonzero is its sorted position minus its bin's first one -- no atomic decides a place.  The bins' sizes come from the sorted keys
+// (k_key_ends), the O(bins) offsets and tables stay on the host (the plan keeps them there anyway), and the fill writes straight into the plan's arena.
+namespace {
+
+typedef unsigned long long form_key_t;
+constexpr int kFormElems = 8;            // consecutive elements per thread of the key kernels: one binary search, then a walk
+
+// the last i in [0, n) with start[i] <= e (start: non-decreasing, start[0] <= e): the row / bin that holds element e, empty ones skipped
+__device__ __forceinline__ int last_start_le(const int *start, int n, long long e)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (start[mid] <= e) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// element e of the rows that are not skipped, in CSR order (start[r] = elements before row r; a skipped row is empty in it): key = tile << 13 | position in its row block
+__global__ void k_tp_keys(const int *start, const int *rp, const int *ci, const int *pos_of_row, const int *rb_row0, int n_rb, int m, int cb, int n_cb, long long n,
+                          form_key_t *keys, unsigned *idx)
+{
+    const long long e0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * kFormElems;
+    if (e0 >= n) return;
+    int r = last_start_le(start, m, e0), r_end = start[r + 1], rb = 0, lr = 0, j0 = 0;
+    bool fresh = true;
+    for (long long e = e0; e < min(n, e0 + kFormElems); ++e) {
+        while (e >= r_end) { ++r; r_end = start[r + 1]; fresh = true; }          // (e < n = start[m]: r stays below m)
+        if (fresh) { const int pos = pos_of_row[r]; rb = last_start_le(rb_row0, n_rb, pos); lr = pos - rb_row0[rb]; j0 = rp[r] - start[r]; fresh = false; }
+        const int j = j0 + (int)e;
+        keys[e] = (((form_key_t)rb * (form_key_t)n_cb + (form_key_t)(ci[j] / cb)) << 13) | (form_key_t)lr;
+        idx[e] = (unsigned)j;
+    }
+}
+// element e of the hub rows (hstart[i] = elements before hub row i): key = piece = column block * hub rows + i
+__global__ void k_lcb_keys(const int *hstart, const int *row_id, int nL, const int *rp, const int *ci, int cb, long long n, form_key_t *keys, unsigned *idx)
+{
+    const long long e0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * kFormElems;
+    if (e0 >= n) return;
+    int i = last_start_le(hstart, nL, e0), i_end = hstart[i + 1], j0 = rp[row_id[i]] - hstart[i];
+    for (long long e = e0; e < min(n, e0 + kFormElems); ++e) {
+        while (e >= i_end) { ++i; i_end = hstart[i + 1]; j0 = rp[row_id[i]] - hstart[i]; }
+        const int j = j0 + (int)e;
+        keys[e] = (form_key_t)(ci[j] / cb) * (form_key_t)nL + (form_key_t)i;
+        idx[e] = (unsigned)j;
+    }
+}
+// sorted keys -> end[bin] = one past the last sorted position of every non-empty bin (the others keep their 0)
+__global__ void k_key_ends(const form_key_t *keys, long long n, int shift, int *end)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const form_key_t t = keys[i] >> shift;
+        if (i + 1 == n || (keys[i + 1] >> shift) != t) end[t] = (int)(i + 1);
+    }
+}
+// sorted element i of tile t goes to place k = i - start[t] of the tile: local row, value (and map entry) RB-major at off2[t], local column CB-major at off1[t]
+__global__ void k_tp_fill(const form_key_t *keys, const unsigned *idx, long long n, const int *start, const int *off2, const int *off1, int n_cb, int cb,
+                          const int *ci, const unsigned short *val, const unsigned *src, unsigned short *lcol, unsigned short *lrow, unsigned short *tval, unsigned *tmap)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const form_key_t key = keys[i];
+        const long long t = (long long)(key >> 13);
+        const long long j = idx[i], k = i - start[t];
+        const size_t e2 = (size_t)off2[t] * kTpSeg + (size_t)k, e1 = (size_t)off1[t] * kTpSeg + (size_t)k;
+        const int c = (int)(t % n_cb);
+        lrow[e2] = (unsigned short)(key & 8191u);
+        tval[e2] = val[j];
+        if (tmap) tmap[e2] = map_of(src, j);
+        lcol[e1] = (unsigned short)(ci[j] - c * cb);
+    }
+}
+// RB-major segment s2 of tile t is CB-major segment off1[t] + (s2 - off2[t])
+__global__ void k_tp_dst(const int *off2, const int *off1, int n_tiles, int S, int *dst)
+{
+    for (long long s2 = (long long)blockIdx.x * blockDim.x + threadIdx.x; s2 < S; s2 += (long long)gridDim.x * blockDim.x) {
+        const int t = last_start_le(off2, n_tiles, s2);
+        dst[off1[t] + ((int)s2 - off2[t])] = (int)s2;
+    }
+}
+// sorted element i of piece q goes to ptr[q] + (i - start[q]); W = the value's bits
+template <class W>
+__global__ void k_lcb_fill(const form_key_t *keys, const unsigned *idx, long long n, const int *start, const int *ptr, int nL, int cb,
+                           const int *ci, const W *val, const unsigned *src, unsigned short *lcol, W *lval, unsigned *lmap)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long q = (long long)keys[i], j = idx[i];
+        const size_t e = (size_t)ptr[q] + (size_t)(i - start[q]);
+        const int c = (int)(q / nL);
+        lcol[e] = (unsigned short)(ci[j] - c * cb);
+        lval[e] = val[j];
+        if (lmap) lmap[e] = map_of(src, j);
+    }
+}
+
+inline unsigned grid_for(long long n, int per_thread = 1) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 256ll * per_thread - 1) / (256ll * per_thread), 1 << 20)); }
+
+// scratch of the sort: a failed allocation frees what came before it and answers kDevNoScratch (the caller takes the fetch path), it is not an error
+struct FormScratch {
+    std::vector<void *> all;
+    void *get(size_t bytes)
+    {
+        void *q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        all.push_back(q);
+        return q;
+    }
+    void *release(void *q) { all.erase(std::find(all.begin(), all.end(), q)); return q; }      // the caller owns q from here
+    ~FormScratch() { for (void *q : all) (void)hipFree(q); }
+};
+bool form_scratch_refused()      // test hook of the fallback: DASP_DEVPACK_FORMS=noscratch makes every scratch allocation of these packers "fail"
+{
+    const char *e = std::getenv("DASP_DEVPACK_FORMS");
+    return e && std::strcmp(e, "noscratch") == 0;
+}
+
+// n pairs written by `write_keys(keys, idx)` -> sorted by key (stable), counted per bin (bin = key >> shift, < bins).  out keeps the sorted pairs and every bin's
+// first sorted position on the device; cnt[bin] comes to the host
+template <class WriteKeys>
+int form_sort_count(long long n, long long bins, int shift, WriteKeys write_keys, DevTiles &out, std::vector<int> &cnt)
+{
+    out = DevTiles{};
+    cnt.assign((size_t)std::max<long long>(bins, 0), 0);
+    if (n <= 0 || bins <= 0) return DASP_OK;
+    if (form_scratch_refused()) return kDevNoScratch;
+    using clk = std::chrono::steady_clock;
+    const bool verbose = std::getenv("DASP_VERBOSE") != nullptr;
+    auto tick = clk::now();
+    auto lap = [&](const char *what) {
+        if (!verbose) return;
+        (void)hipDeviceSynchronize();
+        const auto now = clk::now();
+        std::fprintf(stderr, "[dasp forms] %-27s %.3f s\n", what, std::chrono::duration<double>(now - tick).count());
+        tick = now;
+    };
+    int bits = shift + 1;
+    while (bits < 64 && ((form_key_t)(bins - 1) >> (bits - shift)) != 0) ++bits;      // the bits in use
+    FormScratch sc;
+    auto *k0 = static_cast<form_key_t *>(sc.get((size_t)n * sizeof(form_key_t))), *k1 = static_cast<form_key_t *>(sc.get((size_t)n * sizeof(form_key_t)));
+    auto *v0 = static_cast<unsigned *>(sc.get((size_t)n * 4)), *v1 = static_cast<unsigned *>(sc.get((size_t)n * 4));
+    auto *end = static_cast<int *>(sc.get((size_t)bins * 4));
+    if (!k0 || !k1 || !v0 || !v1 || !end) return kDevNoScratch;
+    size_t tmp_bytes = 0;
+    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k0, k1, v0, v1, (int)n, 0, bits) != hipSuccess) { set_error("hipcub radix sort (device packers)"); return DASP_ERR_HIP; }
+    void *tmp = sc.get(tmp_bytes);
+    if (!tmp) return kDevNoScratch;
+    lap("scratch");
+    if (int rc = write_keys(k0, v0)) return rc;
+    HIP_TRYP(hipGetLastError());
+    lap("keys");
+    if (hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, k0, k1, v0, v1, (int)n, 0, bits) != hipSuccess) { set_error("hipcub radix sort (device packers)"); return DASP_ERR_HIP; }
+    lap("stable sort");
+    HIP_TRYP(hipMemset(end, 0, (size_t)bins * 4));
+    hipLaunchKernelGGL(k_key_ends, dim3(grid_for(n)), dim3(256), 0, 0, k1, n, shift, end);
+    HIP_TRYP(hipGetLastError());
+    std::vector<int> h((size_t)bins);
+    HIP_TRYP(hipMemcpy(h.data(), end, (size_t)bins * 4, hipMemcpyDeviceToHost));
+    // the bins are contiguous in the sorted order: a bin starts where the last non-empty one before it ended
+    int prev = 0;
+    for (size_t t = 0; t < h.size(); ++t) { const int e = h[t]; h[t] = prev; if (e) { cnt[t] = e - prev; prev = e; } }
+    HIP_TRYP(hipMemcpy(end, h.data(), (size_t)bins * 4, hipMemcpyHostToDevice));
+    lap("bin counts");
+    auto own = [&](void *q) { sc.release(q); out.keep.emplace_back(q, [](void *r) { (void)hipFree(r); }); };
+    own(k1); own(v1); own(end);
+    out.keys = k1; out.idx = v1; out.start = end; out.n = n; out.bins = bins;
+    return DASP_OK;
+}
+
+// an int array of the host on the device as scratch (nullptr + kDevNoScratch when it does not fit)
+int form_upload(FormScratch &sc, const int *h, size_t n, const int **out)
+{
+    void *q = sc.get(n * 4);
+    if (!q) return kDevNoScratch;
+    if (n) HIP_TRYP(hipMemcpy(q, h, n * 4, hipMemcpyHostToDevice));
+    *out = static_cast<const int *>(q);
+    return DASP_OK;
+}
+
+}  // namespace
+
+bool devpack_forms_enabled()
+{
+    const char *e = std::getenv("DASP_DEVPACK_FORMS");
+    return !(e && std::strcmp(e, "0") == 0);
+}
+
+int devpack_tp_count(const Plan &p, const DevCsr &d, const int *rp, const unsigned char *skip, const std::vector<int> &pos_of_row, int n_cb, DevTiles &out, std::vector<int> &cnt)
+{
+    const TwoPhase &t = p.tp;
+    const int m = p.m, n_rb = t.n_rb();
+    const long long bins = (long long)n_rb * n_cb;
+    long long n = p.nnz;
+    std::vector<int> start;
+    if (skip) {      // the rows that stay, compacted
+        start.resize((size_t)m + 1);
+        long long run = 0;
+        for (int r = 0; r < m; ++r) { start[(size_t)r] = (int)run; if (!skip[r]) run += rp[r + 1] - rp[r]; }
+        start[(size_t)m] = (int)run;
+        n = run;
+    }
+    return form_sort_count(n, bins, 13, [&](form_key_t *keys, unsigned *idx) -> int {
+        FormScratch sc;
+        const int *d_start = d.rp, *d_pos = nullptr, *d_rb = nullptr;
+        if (skip) if (int rc = form_upload(sc, start.data(), start.size(), &d_start)) return rc;
+        if (int rc = form_upload(sc, pos_of_row.data(), pos_of_row.size(), &d_pos)) return rc;
+        if (int rc = form_upload(sc, t.rb_row0.data(), t.rb_row0.size(), &d_rb)) return rc;
+        hipLaunchKernelGGL(k_tp_keys, dim3(grid_for(n, kFormElems)), dim3(256), 0, 0, d_start, d.rp, d.ci, d_pos, d_rb, n_rb, m, t.cb, n_cb, n, keys, idx);
+        HIP_TRYP(hipGetLastError());
+        HIP_TRYP(hipDeviceSynchronize());      // (the uploads above end with this scope)
+        return DASP_OK;
+    }, out, cnt);
+}
+
+int devpack_lcb_count(const Plan &p, const DevCsr &d, const int *rp, DevTiles &out, std::vector<int> &cnt)
+{
+    const LongCB &L = p.lcb;
+    const int nL = L.n_rows();
+    std::vector<int> hstart((size_t)nL + 1, 0);
+    long long n = 0;
+    for (int i = 0; i < nL; ++i) { hstart[(size_t)i] = (int)n; n += rp[L.row_id[(size_t)i] + 1] - rp[L.row_id[(size_t)i]]; }
+    hstart[(size_t)nL] = (int)n;
+    return form_sort_count(n, (long long)L.n_cb * nL, 0, [&](form_key_t *keys, unsigned *idx) -> int {
+        FormScratch sc;
+        const int *d_hs = nullptr, *d_id = nullptr;
+        if (int rc = form_upload(sc, hstart.data(), hstart.size(), &d_hs)) return rc;
+        if (int rc = form_upload(sc, L.row_id.data(), L.row_id.size(), &d_id)) return rc;
+        hipLaunchKernelGGL(k_lcb_keys, dim3(grid_for(n, kFormElems)), dim3(256), 0, 0, d_hs, d_id, nL, d.rp, d.ci, L.cb, n, keys, idx);
+        HIP_TRYP(hipGetLastError());
+        HIP_TRYP(hipDeviceSynchronize());
+        return DASP_OK;
+    }, out, cnt);
+}
+
+// the streams of Plan::lcb into the arena of an uploaded plan (upload.cpp placed them and sent the tables): pads first, then every element of the sorted pieces
+static int lcb_fill(Plan &p, const DevCsr &d, const DevTiles &s)
+{
+    const LongCB &L = p.lcb;
+    DevicePlan &dp = *p.dev;
+    if (L.n_rows() == 0 || L.elems == 0) return DASP_OK;
+    const size_t vb = (size_t)p.geo.vbytes;
+    auto *lval = const_cast<void *>(dp.lcb.val);
+    auto *lcol = const_cast<unsigned short *>(dp.lcb.lcol);
+    HIP_TRYP(hipMemset(lval, 0, L.elems * vb));
+    HIP_TRYP(hipMemset(lcol, 0xFF, L.elems * 2));          // kLcbPadCol
+    unsigned *lmap = nullptr;
+    if (p.value_map) {
+        HIP_TRYP(hipMalloc(&dp.pk_map[6], L.elems * 4));
+        lmap = static_cast<unsigned *>(dp.pk_map[6]);
+        HIP_TRYP(hipMemset(lmap, 0, L.elems * 4));
+    }
+    if (s.n > 0) {
+        if (vb == 8)
+            hipLaunchKernelGGL((k_lcb_fill<unsigned long long>), dim3(grid_for(s.n)), dim3(256), 0, 0, s.keys, s.idx, s.n, s.start, dp.lcb.ptr, L.n_rows(), L.cb, d.ci,
+                               static_cast<const unsigned long long *>(d.val), d.src, lcol, static_cast<unsigned long long *>(lval), lmap);
+        else
+            hipLaunchKernelGGL((k_lcb_fill<unsigned short>), dim3(grid_for(s.n)), dim3(256), 0, 0, s.keys, s.idx, s.n, s.start, dp.lcb.ptr, L.n_rows(), L.cb, d.ci,
+                               static_cast<const unsigned short *>(d.val), d.src, lcol, static_cast<unsigned short *>(lval), lmap);
+        HIP_TRYP(hipGetLastError());
+    }
+    HIP_TRYP(hipDeviceSynchronize());
+    return DASP_OK;
+}
+
+int devpack_finish_two_phase(Plan &p, const DevCsr &d, const DevTiles &tp, const std::vector<long long> &off2, const std::vector<long long> &off1, const DevTiles &lcb)
+{
+    // the segment offsets as the kernels index them (< 2^30 segments: build_two_phase_device checked), before anything of the plan's is allocated
+    FormScratch sc;
+    const size_t n_tiles = off1.size(), S = p.tp.segments;
+    const int *d_off2 = nullptr, *d_off1 = nullptr;
+    if (S > 0) {
+        std::vector<int> h(off2.begin(), off2.end());
+        if (int rc = form_upload(sc, h.data(), h.size(), &d_off2)) return rc;
+        h.assign(off1.begin(), off1.end());
+        if (int rc = form_upload(sc, h.data(), h.size(), &d_off1)) return rc;
+    }
+    // the arena: the layout upload_plan gives a two-phase plan, every table of the host sent, the nnz-sized streams left for the kernels below, tp_xs zeroed
+    if (int rc = upload_plan_unpacked(p)) return rc;
+    DevicePlan &dp = *p.dev;
+    if (S > 0) {
+        auto *lcol = const_cast<unsigned short *>(dp.tp.lcol), *lrow = const_cast<unsigned short *>(dp.tp.lrow);
+        auto *tval = static_cast<unsigned short *>(const_cast<void *>(dp.tp.val));
+        HIP_TRYP(hipMemset(lcol, 0, S * kTpSeg * 2));           // pads: column 0, row kTpPadRow, value 0, map 0
+        HIP_TRYP(hipMemset(lrow, 0xFF, S * kTpSeg * 2));
+        HIP_TRYP(hipMemset(tval, 0, S * kTpSeg * 2));
+        unsigned *tmap = nullptr;
+        if (p.value_map) {
+            HIP_TRYP(hipMalloc(&dp.pk_map[5], S * kTpSeg * 4));
+            tmap = static_cast<unsigned *>(dp.pk_map[5]);
+            HIP_TRYP(hipMemset(tmap, 0, S * kTpSeg * 4));
+        }
+        const int n_cb = std::max(1, (p.n + p.tp.cb - 1) / p.tp.cb);
+        if (tp.n > 0) hipLaunchKernelGGL(k_tp_fill, dim3(grid_for(tp.n)), dim3(256), 0, 0, tp.keys, tp.idx, tp.n, tp.start, d_off2, d_off1, n_cb, p.tp.cb, d.ci,
+                                         static_cast<const unsigned short *>(d.val), d.src, lcol, lrow, tval, tmap);
+        HIP_TRYP(hipGetLastError());
+        hipLaunchKernelGGL(k_tp_dst, dim3(grid_for((long long)S)), dim3(256), 0, 0, d_off2, d_off1, (int)n_tiles, (int)S, const_cast<int *>(dp.tp.dst));
+        HIP_TRYP(hipGetLastError());
+    }
+    if (int rc = lcb_fill(p, d, lcb)) return rc;
+    HIP_TRYP(hipDeviceSynchronize());
+    p.host_dropped = true;       // no host copies of the streams exist
+    if (p.value_map) return value_map_upload(p);
+    return DASP_OK;
+}
+
+int devpack_finish_panels_lcb(Plan &p, const DevCsr &d, const DevTiles &lcb)
+{
+    if (int rc = upload_plan_unpacked(p)) return rc;      // (the panels are on the device already: this makes the parent's arena -- partial results, then Plan::lcb)
+    if (int rc = lcb_fill(p, d, lcb)) return rc;
+    p.host_dropped = true;       // no host copies of the hub rows' streams exist
+    if (p.value_map) return value_map_upload(p);
+    return DASP_OK;
+}
+
 int devpack_finish_panels(Plan &p) { return upload_plan(p); }
 // the two-phase form of a device-resident CSR: its tile sort runs on the host for now (preprocessing, not the hot path) -- the column ids and values
 // are copied over once, the plan is packed by build_two_phase and uploaded like any host-built plan
@@ -881,10 +1209,10 @@ static void collect_runs(Plan &p, std::vector<HostRun> &out)
         add(am ? am->rt_val : 0, q.rt_map, q.rt_val, q.cnt_rt, 4);
     };
     auto off_in = [&](const void *ptr) -> size_t { return p.dev && ptr ? (size_t)(static_cast<const char *>(ptr) - static_cast<const char *>(p.dev->arena)) : 0; };
-    if (p.two_phase) { if (p.tp.segments) out.push_back({&p, off_in(p.dev ? p.dev->tp.val : nullptr), &p.tp.map, &p.tp.val, p.tp.segments * kTpSeg, nullptr}); }
+    if (p.two_phase) { if (p.tp.segments) out.push_back({&p, off_in(p.dev ? p.dev->tp.val : nullptr), &p.tp.map, &p.tp.val, p.tp.segments * kTpSeg, p.dev ? p.dev->pk_map[5] : nullptr}); }
     else if (!p.panels.empty()) for (auto &h : p.panels) plain(h->impl);
     else plain(p);
-    if (p.lcb.n_rows() > 0 && p.lcb.elems) out.push_back({&p, off_in(p.dev ? p.dev->lcb.val : nullptr), &p.lcb.map, &p.lcb.val, p.lcb.elems, nullptr});
+    if (p.lcb.n_rows() > 0 && p.lcb.elems) out.push_back({&p, off_in(p.dev ? p.dev->lcb.val : nullptr), &p.lcb.map, &p.lcb.val, p.lcb.elems, p.dev ? p.dev->pk_map[6] : nullptr});
 }
 
 static void packer_maps_free(DevicePlan *d)
@@ -1073,6 +1401,11 @@ int download_array(Plan &p, const char *name, void *dst, size_t bytes)
     if (std::strcmp(name, "lcb_val") == 0 && p.dev->lcb.val) {      // column-blocked long rows of a column-panel parent or of a two-phase plan
         if (bytes != p.lcb.elems * vb) { set_error("size mismatch for lcb_val"); return DASP_ERR_ARG; }
         if (bytes) HIP_TRYP(hipMemcpy(dst, p.dev->lcb.val, bytes, hipMemcpyDeviceToHost));
+        return DASP_OK;
+    }
+    if (std::strcmp(name, "lcb_lcol") == 0 && p.dev->lcb.lcol) {
+        if (bytes != p.lcb.elems * 2) { set_error("size mismatch for lcb_lcol"); return DASP_ERR_ARG; }
+        if (bytes) HIP_TRYP(hipMemcpy(dst, p.dev->lcb.lcol, bytes, hipMemcpyDeviceToHost));
         return DASP_OK;
     }
     if (p.two_phase) {      // the tile streams of a two-phase plan (tp_xs: what phase 1 wrote in the last product)

@@ -39,17 +39,55 @@ int decide_long_cb(const Plan &p, const int *rp, int P, std::vector<unsigned cha
     return rows;
 }
 
-int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const std::vector<unsigned char> &in_lcb, const int *slot_of_row)
+// ---- the parts of the packer that need the row pointer and the pieces' element counts only: shared by the host packer and the device one (build_long_cb_device)
+namespace {
+void lcb_rows(Plan &p, const int *rp, const std::vector<unsigned char> &in_lcb, const int *slot_of_row)
 {
     LongCB &L = p.lcb;
     L = LongCB{};
-    const int m = p.m, vb = p.geo.vbytes, A = kLcbStep;          // a piece is a whole number of steps
     L.cb = lcb_col_block(p); L.n_cb = std::max(1, (p.n + L.cb - 1) / L.cb);
     L.h = 1 << 30;
-    for (int i = 0; i < m; ++i) if (in_lcb[(size_t)i]) { L.row_id.push_back(i); L.row_dst.push_back(slot_of_row ? slot_of_row[i] : i); L.h = std::min(L.h, rp[i + 1] - rp[i]); }
+    for (int i = 0; i < p.m; ++i) if (in_lcb[(size_t)i]) { L.row_id.push_back(i); L.row_dst.push_back(slot_of_row ? slot_of_row[i] : i); L.h = std::min(L.h, rp[i + 1] - rp[i]); }
+}
+// element offsets of the pieces (cnt: elements of every piece, CB-major), each padded to whole steps
+int lcb_offsets(LongCB &L, const std::vector<int> &cnt)
+{
+    const int A = kLcbStep;          // a piece is a whole number of steps
+    L.ptr.assign(cnt.size() + 1, 0);
+    long long run = 0;
+    for (size_t q = 0; q < cnt.size(); ++q) { L.ptr[q] = (int)run; run += (cnt[q] + A - 1) / A * A; if (run >= (1ll << 31) - 64) { set_error("long_cb: too many elements"); return DASP_ERR_ARG; } }
+    L.ptr[cnt.size()] = (int)run;
+    L.elems = (size_t)run;
+    return DASP_OK;
+}
+// units: runs of pieces of one column block with ~kLcbUnitElems elements (and at most kLcbUnitPieces pieces).  DASP_OK, or 1: not representable (L reset)
+int lcb_units(LongCB &L)
+{
+    const int nL = L.n_rows(), n_cb = L.n_cb;
+    for (int c = 0; c < n_cb; ++c) {
+        int q0 = c * nL;
+        const int qe = (c + 1) * nL;
+        while (q0 < qe) {
+            int q1 = q0 + 1;
+            while (q1 < qe && q1 - q0 < kLcbUnitPieces && L.ptr[(size_t)q1] - L.ptr[(size_t)q0] < kLcbUnitElems) ++q1;
+            if (L.ptr[(size_t)q1] > L.ptr[(size_t)q0]) { L.unit.push_back(c); L.unit.push_back(q0); L.unit.push_back(q1); }
+            // the sums of a unit's steps are parked in LDS: a piece beyond cb elements (a row that repeats columns thousands of times) does not fit the slice reserved for them
+            if ((L.ptr[(size_t)q1] - L.ptr[(size_t)q0]) / kLcbStep > kLcbUnitElems / kLcbStep + kLcbUnitPieces) { L = LongCB{}; return 1; }
+            q0 = q1;
+        }
+    }
+    return DASP_OK;
+}
+}  // namespace
+
+int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const std::vector<unsigned char> &in_lcb, const int *slot_of_row)
+{
+    lcb_rows(p, rp, in_lcb, slot_of_row);
+    LongCB &L = p.lcb;
+    const int vb = p.geo.vbytes;
     const int nL = L.n_rows(), n_cb = L.n_cb, cb = L.cb;
     const int threads = resolve_threads(p.opt.host_threads);
-    // elements of every piece (row-parallel), padded to A
+    // elements of every piece (row-parallel), padded to a whole number of steps
     std::vector<int> cnt((size_t)n_cb * (size_t)nL, 0);
     auto rows_par = [&](auto f) {
         const int T = std::max(1, std::min(threads, nL));
@@ -61,11 +99,7 @@ int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const 
         for (auto &t : th) t.join();
     };
     rows_par([&](int i) { const int r = L.row_id[(size_t)i]; for (int j = rp[r]; j < rp[r + 1]; ++j) cnt[(size_t)(ci[j] / cb) * (size_t)nL + (size_t)i]++; });
-    L.ptr.assign((size_t)n_cb * (size_t)nL + 1, 0);
-    long long run = 0;
-    for (size_t q = 0; q < cnt.size(); ++q) { L.ptr[q] = (int)run; run += (cnt[q] + A - 1) / A * A; if (run >= (1ll << 31) - 64) { set_error("long_cb: too many elements"); return DASP_ERR_ARG; } }
-    L.ptr[cnt.size()] = (int)run;
-    L.elems = (size_t)run;
+    if (int rc = lcb_offsets(L, cnt)) return rc;
     try { L.lcol.resize(L.elems); L.val.resize(L.elems * (size_t)vb); if (p.value_map) L.map.assign(L.elems, 0u); }
     catch (const std::bad_alloc &) { set_error("out of host memory"); return DASP_ERR_NOMEM; }
     const char *vsrc = static_cast<const char *>(val);
@@ -84,20 +118,20 @@ int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const 
             for (size_t e = (size_t)L.ptr[q] + (size_t)cnt[q]; e < (size_t)L.ptr[q + 1]; ++e) { L.lcol[e] = kLcbPadCol; std::memset(L.val.data() + e * (size_t)vb, 0, (size_t)vb); }
         }
     });
-    // units: runs of pieces of one column block with ~kLcbUnitElems elements (and at most kLcbUnitPieces pieces)
-    for (int c = 0; c < n_cb; ++c) {
-        int q0 = c * nL;
-        const int qe = (c + 1) * nL;
-        while (q0 < qe) {
-            int q1 = q0 + 1;
-            while (q1 < qe && q1 - q0 < kLcbUnitPieces && L.ptr[(size_t)q1] - L.ptr[(size_t)q0] < kLcbUnitElems) ++q1;
-            if (L.ptr[(size_t)q1] > L.ptr[(size_t)q0]) { L.unit.push_back(c); L.unit.push_back(q0); L.unit.push_back(q1); }
-            // the sums of a unit's steps are parked in LDS: a piece beyond cb elements (a row that repeats columns thousands of times) does not fit the slice reserved for them
-            if ((L.ptr[(size_t)q1] - L.ptr[(size_t)q0]) / kLcbStep > kLcbUnitElems / kLcbStep + kLcbUnitPieces) { L = LongCB{}; return 1; }
-            q0 = q1;
-        }
-    }
-    return DASP_OK;
+    return lcb_units(L);
+}
+
+// the same from a device CSR (dasp_plan_create_device), up to the fill: the tables from the piece counts of devpack.hip
+int build_long_cb_device(Plan &p, const int *rp, const DevCsr &d, const std::vector<unsigned char> &in_lcb, const int *slot_of_row, DevTiles &pieces)
+{
+    lcb_rows(p, rp, in_lcb, slot_of_row);
+    LongCB &L = p.lcb;
+    std::vector<int> cnt;
+    if (int rc = devpack_lcb_count(p, d, rp, pieces, cnt)) { L = LongCB{}; return rc; }
+    int rc = lcb_offsets(L, cnt);
+    if (rc == DASP_OK) rc = lcb_units(L);
+    if (rc != DASP_OK) pieces = DevTiles{};
+    return rc;
 }
 
 bool validate_long_cb(const Plan &p, int n_panels, std::string &why)

@@ -323,45 +323,80 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
             lap("whole-matrix meta");
             // the hybrid (r6): hub rows -- the rule of the column-blocked long rows, decide_long_cb -- leave the two-phase streams for
             // Plan::lcb (x staged in LDS per column block, no atomics on one LDS word per hub row); everything else stays two-phase
+            auto lcb_counters = [&] {
+                const LongCB &L = p.lcb;
+                dasp_stats_t &s = p.stats;
+                s.lcb_rows = L.n_rows(); s.lcb_elems = (long long)L.elems; s.lcb_col_block = L.cb; s.lcb_units = L.n_units();
+                s.n_workgroups += L.n_units() + ceil_div(L.n_rows(), kWavesPerWG);
+                s.data_X += (long long)L.elems * (geo.vbytes + 2) + (long long)L.n_units() * (long long)std::min(L.cb, p.n) * geo.vbytes;
+            };
+            auto hub_rows = [&](std::vector<unsigned char> &in_lcb, std::vector<int> &slot_of_row) -> bool {
+                p.lcb = LongCB{};
+                if (decide_long_cb(p, rp, 2, in_lcb, 4, 128) <= 0) return false;
+                if (p.opt.y_order != DASP_Y_NATURAL) { slot_of_row.resize((size_t)m); for (int i = 0; i < m; ++i) slot_of_row[(size_t)p.order[(size_t)i]] = i; }
+                return true;
+            };
             auto hybrid_then_tp = [&](const int *hci, const T *hval) -> int {
                 std::vector<unsigned char> in_lcb;
-                p.lcb = LongCB{};
-                if (decide_long_cb(p, rp, 2, in_lcb, 4, 128) > 0) {
-                    std::vector<int> slot_of_row;
-                    const bool natural = p.opt.y_order == DASP_Y_NATURAL;
-                    if (!natural) { slot_of_row.resize((size_t)m); for (int i = 0; i < m; ++i) slot_of_row[(size_t)p.order[(size_t)i]] = i; }
-                    const int rc_l = build_long_cb(p, rp, hci, hval, in_lcb, natural ? nullptr : slot_of_row.data());
+                std::vector<int> slot_of_row;
+                if (hub_rows(in_lcb, slot_of_row)) {
+                    const int rc_l = build_long_cb(p, rp, hci, hval, in_lcb, slot_of_row.empty() ? nullptr : slot_of_row.data());
                     if (rc_l == 1) in_lcb.clear();
                     else if (rc_l) return rc_l;
                     lap("hub rows by column block");
                 }
                 const int rc_t = build_two_phase(p, rp, hci, hval, in_lcb.empty() ? nullptr : in_lcb.data());
                 if (rc_t != DASP_OK) { p.lcb = LongCB{}; return rc_t; }
-                if (!in_lcb.empty()) {
-                    const LongCB &L = p.lcb;
-                    dasp_stats_t &s = p.stats;
-                    s.lcb_rows = L.n_rows(); s.lcb_elems = (long long)L.elems; s.lcb_col_block = L.cb; s.lcb_units = L.n_units();
-                    s.n_workgroups += L.n_units() + ceil_div(L.n_rows(), kWavesPerWG);
-                    s.data_X += (long long)L.elems * (geo.vbytes + 2) + (long long)L.n_units() * (long long)std::min(L.cb, p.n) * geo.vbytes;
-                }
+                if (!in_lcb.empty()) lcb_counters();
                 return DASP_OK;
+            };
+            // the same from a device CSR (r8): the hub rows' pieces and the tiles are counted, ranked and written by devpack.hip, the rules and tables are the host's
+            // (build_long_cb_device, build_two_phase_device); nothing nnz-sized crosses to the host.  kDevNoScratch: the packers' scratch did not fit -- nothing is left behind
+            auto hybrid_then_tp_device = [&]() -> int {
+                std::vector<unsigned char> in_lcb;
+                std::vector<int> slot_of_row;
+                DevTiles pieces, tiles;
+                if (hub_rows(in_lcb, slot_of_row)) {
+                    const int rc_l = build_long_cb_device(p, rp, *dev, in_lcb, slot_of_row.empty() ? nullptr : slot_of_row.data(), pieces);
+                    if (rc_l == 1) in_lcb.clear();
+                    else if (rc_l) return rc_l;
+                    lap("hub rows by column block (device)");
+                }
+                std::vector<long long> off2, off1;
+                int rc_t = build_two_phase_device(p, rp, *dev, in_lcb.empty() ? nullptr : in_lcb.data(), tiles, off2, off1);
+                lap("two-phase tiles (device)");
+                if (rc_t == DASP_OK) {
+                    if (!in_lcb.empty()) lcb_counters();
+                    rc_t = devpack_finish_two_phase(p, *dev, tiles, off2, off1, pieces);
+                    lap("two-phase streams (device)");
+                }
+                if (rc_t != DASP_OK) { release_device(p); p.lcb = LongCB{}; p.tp = TwoPhase{}; p.two_phase = false; p.host_dropped = false; }
+                return rc_t;
             };
             int rc2;
             if (!dev) { rc2 = hybrid_then_tp(ci, val); lap("two-phase streams"); if (rc2 != kTpDeclined) return rc2; }
             else {
-                raw_vector<int> hci((size_t)nnz);
-                raw_vector<T> hval((size_t)nnz);
-                raw_vector<uint32_t> hsrc;
-                if (int rc = devpack_fetch_csr(p, *dev, hci.data(), hval.data())) return rc;
-                if (p.value_map && dev->src) {      // a column-sorted device CSR: its map entries travel too (else the host's own index + 1 is the map)
-                    hsrc.resize((size_t)nnz);
-                    if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(hsrc.data()), nullptr)) return rc;
-                    p.map_src = hsrc.data();
+                rc2 = devpack_forms_enabled() ? hybrid_then_tp_device() : kDevNoScratch;
+                if (rc2 == kDevNoScratch) {
+                    // the fallback (DASP_DEVPACK_FORMS=0, or no room for the packers' scratch): the column ids and values are copied over once, the plan is packed by
+                    // the host packers and uploaded like any host-built plan; Plan::csr_fetch_bytes says so
+                    raw_vector<int> hci((size_t)nnz);
+                    raw_vector<T> hval((size_t)nnz);
+                    raw_vector<uint32_t> hsrc;
+                    if (int rc = devpack_fetch_csr(p, *dev, hci.data(), hval.data())) return rc;
+                    p.csr_fetch_bytes += (long long)nnz * (4 + (long long)sizeof(T));
+                    if (p.value_map && dev->src) {      // a column-sorted device CSR: its map entries travel too (else the host's own index + 1 is the map)
+                        hsrc.resize((size_t)nnz);
+                        if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(hsrc.data()), nullptr)) return rc;
+                        p.csr_fetch_bytes += (long long)nnz * 4;
+                        p.map_src = hsrc.data();
+                    }
+                    rc2 = hybrid_then_tp(hci.data(), hval.data());
+                    p.map_src = nullptr;      // (hsrc ends here)
+                    lap("two-phase streams (device CSR fetched)");
+                    if (rc2 == DASP_OK) return devpack_finish_panels(p);       // a device-built plan comes back uploaded
                 }
-                rc2 = hybrid_then_tp(hci.data(), hval.data());
-                p.map_src = nullptr;      // (hsrc ends here)
-                lap("two-phase streams (device CSR fetched)");
-                if (rc2 == DASP_OK) return devpack_finish_panels(p);       // a device-built plan comes back uploaded
+                if (rc2 == DASP_OK) return DASP_OK;
                 if (rc2 != kTpDeclined) return rc2;
             }
             // declined by the padding guard (automatic rule only): the matrix keeps its DASP form -- column panels where the rule asked for them, else the plain plan below
@@ -1483,7 +1518,7 @@ static int decide_panels(const Plan &p, const int *rp, const int *ci, const Rema
 template <class T>
 static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int P, const DevCsr *dev)
 {
-    const DevCsr *const dev_in = dev;       // (a device CSR whose long rows go column-blocked is fetched and split on the host: see long_cb below)
+    const DevCsr *const dev_in = dev;       // (the fallback of the hub rows' device packer fetches the CSR and splits it on the host: see long_cb below)
     using clk = std::chrono::steady_clock;
     const auto t_begin = clk::now();
     const bool verbose = std::getenv("DASP_VERBOSE") != nullptr;
@@ -1521,18 +1556,23 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     raw_vector<T> lcb_val;
     raw_vector<uint32_t> lcb_src;
     p.lcb = LongCB{};
+    DevTiles lcb_pieces;      // device path: the hub rows' sorted pieces, from the count here to the fill into the parent's arena (devpack_finish_panels_lcb)
     if (decide_long_cb(p, rp, P, in_lcb) > 0) {
-        if (dev) {      // their cut by column block runs on the host for now: fetch the nonzeros once, then the host split below
+        int rc_lcb = kDevNoScratch;
+        if (dev && devpack_forms_enabled()) rc_lcb = build_long_cb_device(p, rp, *dev, in_lcb, natural ? nullptr : slot_of_row.data(), lcb_pieces);
+        if (dev && rc_lcb == kDevNoScratch) {      // the fallback (DASP_DEVPACK_FORMS=0, or no room for the packer's scratch): fetch the nonzeros once, then the host packer and the host split below
             lcb_ci.resize((size_t)p.nnz); lcb_val.resize((size_t)p.nnz);
             if (int rc = devpack_fetch_csr(p, *dev, lcb_ci.data(), lcb_val.data())) return rc;
+            p.csr_fetch_bytes += (long long)p.nnz * (4 + (long long)sizeof(T));
             if (p.value_map && dev->src) {      // (see the two-phase fetch in build_impl)
                 lcb_src.resize((size_t)p.nnz);
                 if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(lcb_src.data()), nullptr)) return rc;
+                p.csr_fetch_bytes += (long long)p.nnz * 4;
                 p.map_src = lcb_src.data();
             }
             ci = lcb_ci.data(); val = lcb_val.data(); dev = nullptr;
         }
-        const int rc_lcb = build_long_cb(p, rp, ci, val, in_lcb, natural ? nullptr : slot_of_row.data());
+        if (!dev) rc_lcb = build_long_cb(p, rp, ci, val, in_lcb, natural ? nullptr : slot_of_row.data());
         if (rc_lcb == 1) in_lcb.clear();          // (a piece too long for the kernel's LDS slice: the rows stay in the panels)
         else if (rc_lcb) return rc_lcb;
         lap("long rows by column block");
@@ -1567,7 +1607,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
         R.cnt = (size_t)run;
     };
     if (dev) {
-        if (int rc = devpack_panel_split(p, *dev, bnd, P, rpP, devP, dev_keep)) return rc;
+        if (int rc = devpack_panel_split_masked(p, *dev, bnd, P, rpP, devP, dev_keep, lcb_on ? in_lcb.data() : nullptr)) return rc;
         if (rt_max > 0) {
             // the split's row pointers -> lengths, cut, -> the pointers of what is left; the device moves the elements (devpack.hip)
             parallel_for(P, threads, 1, [&](long long k0, long long k1) {
@@ -1715,7 +1755,9 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
         // values + local columns streamed, every unit's slice of x, the partials written and read
         s.data_X += (long long)L.elems * (vb + 2) + (long long)L.n_units() * std::min<long long>(L.cb, xlen) * vb + 2ll * L.n_cb * L.n_rows() * 8;
     }
-    if (dev_in) { if (int rc = devpack_finish_panels(p)) return rc; }      // a device-built plan comes back uploaded: the parent's partial-result buffers too
+    // a device-built plan comes back uploaded: the parent's partial-result buffers too, and the hub rows' streams written behind them
+    if (dev && lcb_on) { if (int rc = devpack_finish_panels_lcb(p, *dev, lcb_pieces)) return rc; }
+    else if (dev_in) { if (int rc = devpack_finish_panels(p)) return rc; }
     lap("parent upload");
     s.pre_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
     return DASP_OK;

@@ -345,6 +345,9 @@ struct Plan {
     bool loaded = false;               // from dasp_plan_load (plan files carry no map)
 
     bool host_dropped = false;
+    // dasp_plan_create_device: bytes of the caller's nnz-sized device arrays (column ids, values, map entries) that were copied to the host while this plan
+    // was built -- 0 unless a form took the host packers (DASP_DEVPACK_FORMS=0, or the device packers' scratch did not fit)
+    long long csr_fetch_bytes = 0;
     DevicePlan *dev = nullptr;
 
     ~Plan();
@@ -369,7 +372,27 @@ int devpack_chunk_spans(const Plan &p, const DevCsr &d, const raw_vector<int> &r
                         const std::vector<int> &nchunks, int *k16, unsigned long long *narrow_mask);      // narrow_mask: nullptr or [blocks] (plan.cpp)
 int devpack_all(Plan &p, const DevCsr &d, const PackMeta &m);
 int devpack_finish_panels(Plan &p);
-int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val);      // column ids and values of a device CSR -> host arrays of nnz elements (val nullptr: the ids only)
+int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val);      // column ids and values of a device CSR -> host arrays of nnz elements (val nullptr: the ids only); the caller counts them in Plan::csr_fetch_bytes
+// ---- the two-phase streams and the column-blocked long rows of a device CSR (r8).  Both packers rank a nonzero inside its bin (a two-phase tile, a piece of a
+// hub row) the way the host packers' serial walks do, by a STABLE radix sort of (key, CSR index) pairs whose input order is the CSR's: key = bin << shift | the row's
+// position inside its row block (two-phase), or the bin alone (pieces).  DevTiles = the sorted pairs and every bin's first sorted position, kept on the device from
+// the count (which the host's O(bins) tables need) to the fill (which needs the plan's arena)
+struct DevTiles {
+    const unsigned long long *keys = nullptr; const uint32_t *idx = nullptr; const int *start = nullptr;      // device: [n] sorted keys, their CSR indices; [bins] first position
+    long long n = 0, bins = 0;
+    std::vector<std::shared_ptr<void>> keep;
+};
+constexpr int kDevNoScratch = 2;        // a scratch allocation of these packers failed (nothing is left behind): the caller takes the fetch path
+bool devpack_forms_enabled();           // DASP_DEVPACK_FORMS (A/B knob, read at every call): 0 = the fetch path
+// nonzeros per (row block, column block) tile of the rows that are not skipped; pos_of_row[row] = its output position; p.tp.rb_row0 / cb are set
+int devpack_tp_count(const Plan &p, const DevCsr &d, const int *rp, const unsigned char *skip, const std::vector<int> &pos_of_row, int n_cb, DevTiles &out, std::vector<int> &cnt);
+// elements per (column block, hub row) piece; p.lcb.row_id / cb / n_cb are set
+int devpack_lcb_count(const Plan &p, const DevCsr &d, const int *rp, DevTiles &out, std::vector<int> &cnt);
+// a two-phase plan (with or without hub rows): the arena, then the streams written into it (off2 / off1: build_two_phase's segment offsets); comes back uploaded
+int devpack_finish_two_phase(Plan &p, const DevCsr &d, const DevTiles &tp, const std::vector<long long> &off2, const std::vector<long long> &off1, const DevTiles &lcb);
+// devpack_finish_panels for a parent with column-blocked long rows: the upload, then their streams written into the arena
+int devpack_finish_panels_lcb(Plan &p, const DevCsr &d, const DevTiles &lcb);
+void release_device(Plan &p);           // upload.cpp: frees Plan::dev
 // the calling thread's HIP device / make `device` the calling thread's (panel workers of a device-built plan)
 int devpack_current_device();
 void devpack_use_device(int device);
@@ -378,6 +401,9 @@ int devpack_gather_columns(const Plan &p, const DevCsr &d, const std::vector<lon
 // column-panel split of a device CSR: P sub-matrices by column range (remapped columns, row order kept); `keep` owns the device arrays
 int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
                         std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep);
+// the same with a row mask (nullptr: none): mask[row] != 0 = the row is empty in every panel (the hub rows of Plan::lcb)
+int devpack_panel_split_masked(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
+                               std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep, const unsigned char *mask);
 
 // row tiles of a device-built column panel (plan.cpp build_panels): `panel` = the split's sub-matrix, rp_rest = the row pointer of the rows that
 // stay with the panel's plan (host), at[row] = first element of a tiled row in the tiles' arrays (-1: not tiled), cnt = their elements.
@@ -412,6 +438,9 @@ inline int win_fold_tiles(int n_windows, int n_short_tiles)
 }
 constexpr int kTpDeclined = 1;          // build_two_phase under the automatic rule: the padded streams would pass 3 x the nonzeros (or the tile table 64 M entries) -- not an error
 int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, const unsigned char *skip = nullptr);
+// the same plan from a device CSR, up to the fill: every rule, table and counter of build_two_phase from the device's tile counts; `tiles`, off2 and off1 are what
+// devpack_finish_two_phase needs.  DASP_OK, kTpDeclined, kDevNoScratch or an error
+int build_two_phase_device(Plan &p, const int *rp, const DevCsr &d, const unsigned char *skip, DevTiles &tiles, std::vector<long long> &off2, std::vector<long long> &off1);
 // value map entry of nonzero j of the CSR the packers read (Plan::map_src)
 inline uint32_t map_entry(const Plan &p, long long j) { return p.map_src ? p.map_src[j] : (uint32_t)(j + 1); }
 bool validate_two_phase(const Plan &p, std::string &why);
@@ -419,6 +448,8 @@ bool validate_two_phase(const Plan &p, std::string &why);
 // column-blocked long rows (longcb.cpp): which rows (in_lcb[row] = 1) a column-panel plan of P panels hands to them (0 rows: none), the packer, the checks
 int decide_long_cb(const Plan &p, const int *rp, int P, std::vector<unsigned char> &in_lcb, int share_den = 4, int per_block = 64);
 int build_long_cb(Plan &p, const int *rp, const int *ci, const void *val, const std::vector<unsigned char> &in_lcb, const int *slot_of_row);      // DASP_OK, an error, or 1: not representable (p.lcb left empty)
+// the same from a device CSR, up to the fill (devpack_finish_two_phase / devpack_finish_panels): tables from the device's piece counts.  DASP_OK, 1, kDevNoScratch or an error
+int build_long_cb_device(Plan &p, const int *rp, const DevCsr &d, const std::vector<unsigned char> &in_lcb, const int *slot_of_row, DevTiles &pieces);
 bool validate_long_cb(const Plan &p, int n_panels, std::string &why);
 
 // loader (mmio.cpp).  val_out: malloc'd array of double or binary16.

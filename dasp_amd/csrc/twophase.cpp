@@ -6,6 +6,8 @@
 #include <atomic>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -45,35 +47,121 @@ int decide_two_phase(const Plan &p, const int *rp, int scattered)
     return scattered ? 1 : 0;
 }
 
+// ---- the parts of the packer that need row lengths and tile counts only: shared by the host packer and the device one (build_two_phase_device), so that both take
+// the same decisions, write the same tables and report the same errors
+namespace {
+using tp_clock = std::chrono::steady_clock;
+
+int tp_check_args(const Plan &p, int *cb_out, int *rbm_out)
+{
+    if (p.precision != 16) { set_error("two_phase: f16 plans only"); return DASP_ERR_ARG; }
+    if (p.opt.n_parts > 0) { set_error("two_phase: not with a column remap (n_parts)"); return DASP_ERR_ARG; }
+    const int cb = p.opt.tp_col_block > 0 ? p.opt.tp_col_block : kTpColBlock;
+    const int rbm = p.opt.tp_row_block > 0 ? p.opt.tp_row_block : kTpRowBlock;
+    if (cb % 8 || cb < 8 || cb > 65536) { set_error("tp_col_block must be a multiple of 8 in 8 .. 65536"); return DASP_ERR_ARG; }
+    if (rbm < 1 || rbm > 8192) { set_error("tp_row_block must be in 1 .. 8192"); return DASP_ERR_ARG; }
+    *cb_out = cb; *rbm_out = rbm;
+    return DASP_OK;
+}
+
+inline long long tp_sample_stride(long long nnz) { return std::max<long long>(1, nnz >> 22); }              // <= ~4 M samples
+// auto: half-size column blocks when the columns are skewed -- one block of 32768 holding several times its share of the nonzeros (R-MAT: the heaviest holds 19 %, 12 x
+// the mean; the other stand-ins 1.0-1.3 x).  rmat_2M f16 0.0893 -> 0.0826 ms; every even family prefers 32768 (fewer tiles, less padding: ljournal-2008 0.1745 / 0.1891,
+// webbase-1M x4 0.0529 / 0.0690: tools/scratch/tp_blocks_sweep2.sh).  sample(i) = the column id of nonzero i * tp_sample_stride(nnz)
+template <class Sample>
+int tp_auto_col_block(int n, long long nnz, Sample sample)
+{
+    const int nb = std::max(1, (n + kTpColBlock - 1) / kTpColBlock);
+    std::vector<long long> hist((size_t)nb, 0);
+    const long long stride = tp_sample_stride(nnz);
+    long long taken = 0;
+    for (long long j = 0; j < nnz; j += stride) { hist[(size_t)(sample(taken) / kTpColBlock)]++; ++taken; }
+    const long long heaviest = *std::max_element(hist.begin(), hist.end());
+    return nb >= 8 && heaviest * nb > 4 * taken ? kTpColBlock / 2 : kTpColBlock;
+}
+
+// ---- row blocks: consecutive output positions, <= rbm of them, about `target` nonzeros each (the permuted order is sorted by row
+// length: equal counts of rows would give the first blocks a hundred times the work of the last).  Returns the nonzeros of the rows that are not skipped
+template <class LenOf, class RowAt>
+long long tp_row_blocks(TwoPhase &t, int m, long long nnz, int rbm, LenOf len_of, RowAt row_at)
+{
+    const long long target = std::max<long long>(16384, std::min<long long>(1 << 17, nnz / 1024 + 1));
+    t.rb_row0.push_back(0);
+    long long acc = 0; int rows = 0;
+    for (int pos = 0; pos < m; ++pos) {
+        const int r = row_at(pos);
+        const int len = len_of(r);
+        if (rows > 0 && (rows >= rbm || acc + len > target)) { t.rb_row0.push_back(pos); acc = 0; rows = 0; }
+        acc += len; ++rows;
+    }
+    if (m > 0) t.rb_row0.push_back(m);
+    long long nnz_here = 0;
+    for (int r = 0; r < m; ++r) nnz_here += len_of(r);
+    return nnz_here;
+}
+
+inline long long tp_segs_of(int cnt) { return (long long)((cnt + kTpSeg - 1) / kTpSeg); }
+// ---- segment offsets: off2 = RB-major (row block, then column block), off1 = CB-major (column block, then row block); sets t.segments and t.rb_seg0.
+// DASP_OK, kTpDeclined (t reset) or an error
+int tp_offsets(TwoPhase &t, const std::vector<int> &cnt, int n_rb, int n_cb, bool may_decline, long long nnz_here, std::vector<long long> &off2, std::vector<long long> &off1)
+{
+    off2.assign((size_t)n_rb * (size_t)n_cb + 1, 0); off1.assign((size_t)n_rb * (size_t)n_cb, 0);
+    long long run = 0;
+    for (size_t i = 0; i < cnt.size(); ++i) { off2[i] = run; run += tp_segs_of(cnt[i]); }
+    off2[cnt.size()] = run;
+    long long run1 = 0;
+    for (int c = 0; c < n_cb; ++c)
+        for (int b = 0; b < n_rb; ++b) { const size_t i = (size_t)b * (size_t)n_cb + (size_t)c; off1[i] = run1; run1 += tp_segs_of(cnt[i]); }
+    if (run != run1) { set_error("two_phase: internal offset mismatch"); return DASP_ERR_STATE; }
+    if (may_decline && run * kTpSeg > 3 * nnz_here) { t = TwoPhase{}; return kTpDeclined; }
+    if (run >= (1ll << 31) / 2) { set_error("two_phase: too many segments for 32-bit segment indices"); return DASP_ERR_ARG; }
+    t.segments = (size_t)run;
+    t.rb_seg0.resize((size_t)n_rb + 1);
+    for (int b = 0; b <= n_rb; ++b) t.rb_seg0[(size_t)b] = (int)off2[std::min((size_t)b * (size_t)n_cb, cnt.size())];
+    return DASP_OK;
+}
+
+// ---- phase-1 units (runs of <= kTpUnitSegs segments inside one column block) and the counters: the classifier's stay (whole matrix); the native sizes describe this form
+void tp_units_and_stats(Plan &p, const std::vector<long long> &off1, int n_cb, tp_clock::time_point t_begin)
+{
+    TwoPhase &t = p.tp;
+    const int n_rb = t.n_rb(), m = p.m, n = p.n, vb = p.geo.vbytes, cb = t.cb;
+    const long long nnz = p.nnz;
+    const size_t S = t.segments;
+    for (int c = 0; c < n_cb; ++c) {
+        const long long s0 = n_rb > 0 ? off1[(size_t)c] : 0;
+        const long long s1 = c + 1 < n_cb ? (n_rb > 0 ? off1[(size_t)c + 1] : 0) : (long long)S;
+        for (long long s = s0; s < s1; s += kTpUnitSegs) { t.unit.push_back(c); t.unit.push_back((int)s); t.unit.push_back((int)std::min<long long>(s1, s + kTpUnitSegs)); }
+    }
+    p.two_phase = true;
+    p.cnt_long = p.cnt_reg = p.cnt_irr = p.cnt_short = p.cnt_rt = 0;
+    dasp_stats_t &s = p.stats;
+    s.fill0_nnz_short = s.fill0_nnz_long = 0; s.fill0_nnz_reg = (long long)S * kTpSeg;
+    s.n_med_blocks = s.n_long_pieces = s.n_long_multi = s.n_short_tiles = 0;
+    s.n_workgroups = t.n_units() + n_rb;
+    s.x_window_on = s.n_windows = s.n_windows_lds = s.lds_bytes = s.row_window = s.cid16_on = s.x_window_hybrid = s.chunk_pairs = s.cid8_chunks = 0;
+    s.med_rows_as_pieces = s.short_seg = s.row_tile_max = s.n_row_tiles = 0; s.row_tile_nnz = 0; s.n_col_panels = 0; s.window_nnz_frac = 0.0;
+    s.rate_fill0 = nnz > 0 ? (double)((long long)S * kTpSeg + (long long)p.lcb.elems - nnz) / (double)nnz : 0.0;
+    // streamed per SpMV: local columns + xs written (phase 1), values + local rows + xs read (phase 2), the segment map, every unit's slice of x, y
+    s.data_X = (long long)S * kTpSeg * (2 + vb + vb + 2 + vb) + (long long)S * 4 + (long long)t.n_units() * (long long)std::min(cb, n) * vb + (long long)m * vb;
+    s.two_phase = 1; s.tp_col_block = cb; s.tp_row_blocks = n_rb; s.tp_units = t.n_units(); s.tp_segments = (long long)S; s.tp_seg_elems = kTpSeg;
+    s.pre_ms = std::chrono::duration<double, std::milli>(tp_clock::now() - t_begin).count() + s.pre_ms;
+}
+}  // namespace
+
 int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, const unsigned char *skip)
 {
     // skip[row] != 0 (r6, the f16 hybrid): the row's nonzeros are not this form's -- the hub rows of a plan whose Plan::lcb holds them column-blocked; the row keeps its
     // output position and gets y = 0 from phase 2 (dasp_lcb_reduce_kernel stores / adds its sum behind it)
     auto len_of = [&](int r) { return skip && skip[r] ? 0 : rp[r + 1] - rp[r]; };
-    using clk = std::chrono::steady_clock;
-    const auto t_begin = clk::now();
-    if (p.precision != 16) { set_error("two_phase: f16 plans only"); return DASP_ERR_ARG; }
-    if (p.opt.n_parts > 0) { set_error("two_phase: not with a column remap (n_parts)"); return DASP_ERR_ARG; }
+    const auto t_begin = tp_clock::now();
+    int cb = 0, rbm = 0;
+    if (int rc = tp_check_args(p, &cb, &rbm)) return rc;
     const int m = p.m, n = p.n;
     const long long nnz = p.nnz;
     const int vb = p.geo.vbytes;
-    int cb = p.opt.tp_col_block > 0 ? p.opt.tp_col_block : kTpColBlock;
-    int rbm = p.opt.tp_row_block > 0 ? p.opt.tp_row_block : kTpRowBlock;
-    if (cb % 8 || cb < 8 || cb > 65536) { set_error("tp_col_block must be a multiple of 8 in 8 .. 65536"); return DASP_ERR_ARG; }
-    if (rbm < 1 || rbm > 8192) { set_error("tp_row_block must be in 1 .. 8192"); return DASP_ERR_ARG; }
     const int threads = resolve_threads(p.opt.host_threads);
-    if (p.opt.tp_col_block <= 0 && nnz > 0) {
-        // auto: half-size column blocks when the columns are skewed -- one block of 32768 holding several times its share of the nonzeros (R-MAT: the heaviest holds 19 %, 12 x
-        // the mean; the other stand-ins 1.0-1.3 x).  rmat_2M f16 0.0893 -> 0.0826 ms; every even family prefers 32768 (fewer tiles, less padding: ljournal-2008 0.1745 / 0.1891,
-        // webbase-1M x4 0.0529 / 0.0690: tools/scratch/tp_blocks_sweep2.sh)
-        const int nb = std::max(1, (n + kTpColBlock - 1) / kTpColBlock);
-        std::vector<long long> hist((size_t)nb, 0);
-        const long long stride = std::max<long long>(1, nnz >> 22);              // <= ~4 M samples
-        long long taken = 0;
-        for (long long j = 0; j < nnz; j += stride) { hist[(size_t)(ci[j] / kTpColBlock)]++; ++taken; }
-        const long long heaviest = *std::max_element(hist.begin(), hist.end());
-        if (nb >= 8 && heaviest * nb > 4 * taken) cb = kTpColBlock / 2;
-    }
+    if (p.opt.tp_col_block <= 0 && nnz > 0) { const long long stride = tp_sample_stride(nnz); cb = tp_auto_col_block(n, nnz, [&](long long i) { return ci[i * stride]; }); }
     TwoPhase &t = p.tp;
     t = TwoPhase{};
     t.cb = cb; t.rb_max = rbm;
@@ -81,29 +169,13 @@ int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, cons
     const int *order = p.order.data();                 // output position -> row (permuted order)
     auto row_at = [&](int pos) { return natural ? pos : order[pos]; };
     const int n_cb = std::max(1, (n + cb - 1) / cb);
-
-    // ---- row blocks: consecutive output positions, <= rbm of them, about `target` nonzeros each (the permuted order is sorted by row
-    // length: equal counts of rows would give the first blocks a hundred times the work of the last)
-    const long long target = std::max<long long>(16384, std::min<long long>(1 << 17, nnz / 1024 + 1));
-    t.rb_row0.push_back(0);
-    {
-        long long acc = 0; int rows = 0;
-        for (int pos = 0; pos < m; ++pos) {
-            const int r = row_at(pos);
-            const int len = len_of(r);
-            if (rows > 0 && (rows >= rbm || acc + len > target)) { t.rb_row0.push_back(pos); acc = 0; rows = 0; }
-            acc += len; ++rows;
-        }
-        if (m > 0) t.rb_row0.push_back(m);
-    }
+    const long long nnz_here = tp_row_blocks(t, m, nnz, rbm, len_of, row_at);
     const int n_rb = t.n_rb();
     // the automatic rule's last word: every non-empty (row block, column block) tile is padded to whole 64-element segments, and a row block holds at most
     // rbm rows -- a large, very sparse matrix (50 M rows of 3 nonzeros: 1526 column blocks, ~8 nonzeros per tile) would store several times its nonzeros and keep
     // n_rb * n_cb * 20 bytes of tables on the host.  Declined (kTpDeclined: build_impl goes on to column panels / the plain plan) when the padded streams pass 3 x the
     // nonzeros (webbase-1M x4, 1.59 x padding, wins 53.0 against 61.5 us; x16, 2.69 x, 291.9 against 328.2 us; the form's time follows its padded size, so ~3 x is the break-even there) or the tile table passes 64 M entries; a forced two_phase = 1 is built as asked.
     const bool may_decline = p.opt.two_phase == 0;
-    long long nnz_here = 0;
-    for (int r = 0; r < m; ++r) nnz_here += len_of(r);
     if (may_decline && (long long)n_rb * (long long)n_cb > (1ll << 26)) { t = TwoPhase{}; return kTpDeclined; }
     // ---- nonzeros per tile
     std::vector<int> cnt((size_t)n_rb * (size_t)n_cb, 0);
@@ -114,24 +186,10 @@ int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, cons
             for (int j = rp[r], je = rp[r] + len_of(r); j < je; ++j) c[ci[j] / cb]++;
         }
     });
-    // ---- segment offsets: off2 = RB-major (row block, then column block), off1 = CB-major (column block, then row block)
-    std::vector<long long> off2((size_t)n_rb * (size_t)n_cb + 1), off1((size_t)n_rb * (size_t)n_cb);
-    auto segs_of = [&](size_t i) { return (long long)((cnt[i] + kTpSeg - 1) / kTpSeg); };
-    {
-        long long run = 0;
-        for (size_t i = 0; i < cnt.size(); ++i) { off2[i] = run; run += segs_of(i); }
-        off2[cnt.size()] = run;
-        long long run1 = 0;
-        for (int c = 0; c < n_cb; ++c)
-            for (int b = 0; b < n_rb; ++b) { const size_t i = (size_t)b * (size_t)n_cb + (size_t)c; off1[i] = run1; run1 += segs_of(i); }
-        if (run != run1) { set_error("two_phase: internal offset mismatch"); return DASP_ERR_STATE; }
-        if (may_decline && run * kTpSeg > 3 * nnz_here) { t = TwoPhase{}; return kTpDeclined; }
-        if (run >= (1ll << 31) / 2) { set_error("two_phase: too many segments for 32-bit segment indices"); return DASP_ERR_ARG; }
-        t.segments = (size_t)run;
-    }
+    std::vector<long long> off2, off1;
+    if (int rc = tp_offsets(t, cnt, n_rb, n_cb, may_decline, nnz_here, off2, off1)) return rc;
+    auto segs_of = [&](size_t i) { return tp_segs_of(cnt[i]); };
     const size_t S = t.segments;
-    t.rb_seg0.resize((size_t)n_rb + 1);
-    for (int b = 0; b <= n_rb; ++b) t.rb_seg0[(size_t)b] = (int)off2[std::min((size_t)b * (size_t)n_cb, cnt.size())];
     try {
         t.lcol.resize(S * kTpSeg); t.lrow.resize(S * kTpSeg); t.val.resize(S * kTpSeg * (size_t)vb); t.dst.resize(S);
         if (p.value_map) t.map.assign(S * kTpSeg, 0u);      // pads stay 0
@@ -163,26 +221,51 @@ int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, cons
             for (long long s = 0; s < sg; ++s) t.dst[(size_t)(off1[i] + s)] = (int)(off2[i] + s);
         }
     });
-    // ---- phase-1 units: runs of <= kTpUnitSegs segments inside one column block
-    for (int c = 0; c < n_cb; ++c) {
-        const long long s0 = n_rb > 0 ? off1[(size_t)c] : 0;
-        const long long s1 = c + 1 < n_cb ? (n_rb > 0 ? off1[(size_t)c + 1] : 0) : (long long)S;
-        for (long long s = s0; s < s1; s += kTpUnitSegs) { t.unit.push_back(c); t.unit.push_back((int)s); t.unit.push_back((int)std::min<long long>(s1, s + kTpUnitSegs)); }
+    tp_units_and_stats(p, off1, n_cb, t_begin);
+    return DASP_OK;
+}
+
+// the same plan from a device CSR (dasp_plan_create_device), up to the fill: the O(rows) and O(tiles) steps above on the host, the tile counts from devpack.hip
+int build_two_phase_device(Plan &p, const int *rp, const DevCsr &d, const unsigned char *skip, DevTiles &tiles, std::vector<long long> &off2, std::vector<long long> &off1)
+{
+    auto len_of = [&](int r) { return skip && skip[r] ? 0 : rp[r + 1] - rp[r]; };
+    const auto t_begin = tp_clock::now();
+    const bool verbose = std::getenv("DASP_VERBOSE") != nullptr;
+    auto tick = t_begin;
+    auto lap = [&](const char *what) { if (verbose) { auto now = tp_clock::now(); std::fprintf(stderr, "[dasp two-phase] %-23s %.3f s\n", what, std::chrono::duration<double>(now - tick).count()); tick = now; } };
+    int cb = 0, rbm = 0;
+    if (int rc = tp_check_args(p, &cb, &rbm)) return rc;
+    const int m = p.m, n = p.n;
+    const long long nnz = p.nnz;
+    if (p.opt.tp_col_block <= 0 && nnz > 0) {      // the same strided sample, gathered on the device (<= ~4 M ids)
+        const long long stride = tp_sample_stride(nnz);
+        std::vector<int> fetched;
+        if (int rc = devpack_gather_columns(p, d, nullptr, 0, stride, (nnz + stride - 1) / stride, fetched)) return rc;
+        cb = tp_auto_col_block(n, nnz, [&](long long i) { return fetched[(size_t)i]; });
     }
-    p.two_phase = true;
-    p.cnt_long = p.cnt_reg = p.cnt_irr = p.cnt_short = p.cnt_rt = 0;
-    // ---- counters: the classifier's stay (whole matrix); the native sizes describe this form
-    dasp_stats_t &s = p.stats;
-    s.fill0_nnz_short = s.fill0_nnz_long = 0; s.fill0_nnz_reg = (long long)S * kTpSeg;
-    s.n_med_blocks = s.n_long_pieces = s.n_long_multi = s.n_short_tiles = 0;
-    s.n_workgroups = t.n_units() + n_rb;
-    s.x_window_on = s.n_windows = s.n_windows_lds = s.lds_bytes = s.row_window = s.cid16_on = s.x_window_hybrid = s.chunk_pairs = s.cid8_chunks = 0;
-    s.med_rows_as_pieces = s.short_seg = s.row_tile_max = s.n_row_tiles = 0; s.row_tile_nnz = 0; s.n_col_panels = 0; s.window_nnz_frac = 0.0;
-    s.rate_fill0 = nnz > 0 ? (double)((long long)S * kTpSeg + (long long)p.lcb.elems - nnz) / (double)nnz : 0.0;
-    // streamed per SpMV: local columns + xs written (phase 1), values + local rows + xs read (phase 2), the segment map, every unit's slice of x, y
-    s.data_X = (long long)S * kTpSeg * (2 + vb + vb + 2 + vb) + (long long)S * 4 + (long long)t.n_units() * (long long)std::min(cb, n) * vb + (long long)m * vb;
-    s.two_phase = 1; s.tp_col_block = cb; s.tp_row_blocks = n_rb; s.tp_units = t.n_units(); s.tp_segments = (long long)S; s.tp_seg_elems = kTpSeg;
-    s.pre_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count() + s.pre_ms;
+    TwoPhase &t = p.tp;
+    t = TwoPhase{};
+    t.cb = cb; t.rb_max = rbm;
+    const bool natural = p.opt.y_order == DASP_Y_NATURAL;
+    const int *order = p.order.data();
+    auto row_at = [&](int pos) { return natural ? pos : order[pos]; };
+    const int n_cb = std::max(1, (n + cb - 1) / cb);
+    lap("column-block width");
+    const long long nnz_here = tp_row_blocks(t, m, nnz, rbm, len_of, row_at);
+    lap("row blocks");
+    const int n_rb = t.n_rb();
+    const bool may_decline = p.opt.two_phase == 0;
+    if (may_decline && (long long)n_rb * (long long)n_cb > (1ll << 26)) { t = TwoPhase{}; return kTpDeclined; }
+    if ((long long)n_rb * (long long)n_cb >= (1ll << 31) - 1) { t = TwoPhase{}; return kDevNoScratch; }      // (a forced plan with a tile table the device sort does not index: the host path answers)
+    std::vector<int> pos_of_row((size_t)m);
+    for (int pos = 0; pos < m; ++pos) pos_of_row[(size_t)row_at(pos)] = pos;
+    std::vector<int> cnt;
+    lap("positions of the rows");
+    if (int rc = devpack_tp_count(p, d, rp, skip, pos_of_row, n_cb, tiles, cnt)) { t = TwoPhase{}; return rc; }
+    lap("tile counts (device)");
+    if (int rc = tp_offsets(t, cnt, n_rb, n_cb, may_decline, nnz_here, off2, off1)) { tiles = DevTiles{}; return rc; }
+    tp_units_and_stats(p, off1, n_cb, t_begin);
+    lap("offsets, units");
     return DASP_OK;
 }
 

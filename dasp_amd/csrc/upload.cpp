@@ -77,8 +77,9 @@ static int upload_long_cb(Plan &p, DevicePlan *d, const LcbOffsets &o)
     const LongCB &L = p.lcb;
     const size_t vbytes = (size_t)p.geo.vbytes;
     char *base = static_cast<char *>(d->arena);
-    HIP_TRY(hipMemcpy(base + o.v, L.val.data(), L.elems * vbytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(base + o.c, L.lcol.data(), L.elems * 2, hipMemcpyHostToDevice));
+    // (a plan packed on the device has no host copy of the two streams: devpack.hip writes them into the arena)
+    if (!L.val.empty()) HIP_TRY(hipMemcpy(base + o.v, L.val.data(), L.elems * vbytes, hipMemcpyHostToDevice));
+    if (!L.lcol.empty()) HIP_TRY(hipMemcpy(base + o.c, L.lcol.data(), L.elems * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(base + o.p, L.ptr.data(), L.ptr.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(base + o.u, L.unit.data(), L.unit.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(base + o.d, L.row_dst.data(), L.row_dst.size() * 4, hipMemcpyHostToDevice));
@@ -105,13 +106,18 @@ void choose_long16(Plan &p)
     }
 }
 
+void release_device(Plan &p)
+{
+    if (p.dev) { value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
+}
+
 int upload_plan(Plan &p);
 static int upload_plan_impl(Plan &p)
 {
     if (int rc = require_device()) return rc;
     if (p.host_dropped && p.dev) return DASP_OK;   // already on the device (packed there, or host copies released)
     if (p.host_dropped) { set_error("host arrays were dropped"); return DASP_ERR_STATE; }
-    if (p.dev) { value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
+    release_device(p);
     auto *d = new DevicePlan();
     p.dev = d;
     HIP_TRY(hipGetDevice(&d->device));

@@ -271,7 +271,13 @@ int dasp_plan_create(dasp_plan_t **plan, int precision, int rowA, int colA, int 
 /* the same with the CSR already on the current HIP device (dRowPtr / dColIdx / dVal are device pointers): only the row
  * pointer visits the host; the nonzeros are range-checked, scanned, split into column panels where the plan uses them, and packed by
  * kernels.  The plan comes back uploaded and produces bit-identical packed arrays to dasp_plan_create, with the same
- * automatic choices (only hybrid x windows are decided on a host CSR alone). */
+ * automatic choices (only hybrid x windows are decided on a host CSR alone).  That includes the two-phase streams and the column-blocked long
+ * rows (and the panels beside them): a stable radix sort on the device ranks every nonzero inside its tile / piece as the host packers' serial
+ * walks do.  Such a plan therefore holds NO host copy of its nnz-sized streams, like every other device-built plan: dasp_plan_host_array of
+ * tp_lcol / tp_lrow / tp_val / tp_dst / lcb_val / lcb_lcol answers DASP_ERR_STATE (dasp_plan_download_array reads them), dasp_plan_save refuses;
+ * the small tables (tp_rb_row0, tp_rb_seg0, tp_unit, lcb_ptr, lcb_unit, lcb_row_id, lcb_row_dst, order) stay on the host.  The host packers remain
+ * as the fallback of those two forms only -- when the device packers' scratch (about 24 bytes per nonzero while they run) cannot be allocated, or
+ * DASP_DEVPACK_FORMS=0 is set (read at every call): the column ids and values are then copied to the host once; dasp_plan_csr_fetch_bytes tells. */
 int dasp_plan_create_device(dasp_plan_t **plan, int precision, int rowA, int colA, int nnzA,
                             const int *dRowPtr, const int *dColIdx, const void *dVal, const dasp_options_t *opt);
 /* Placement trials (r3; opt-in since r4): the same packed bytes run the HBM-bound kernels at one of two speeds ~8 % apart depending on where the
@@ -335,6 +341,11 @@ int dasp_plan_update_values(dasp_plan_t *plan, const void *dVal, void *stream);
 int dasp_plan_update_values_host(dasp_plan_t *plan, const void *csrVal);
 /* mapped value slots over all value arrays of the plan (panels included); 0 without a map */
 long long dasp_plan_value_map_slots(const dasp_plan_t *plan);
+/* bytes of the caller's nnz-sized DEVICE arrays (column ids, values, value-map entries) that dasp_plan_create_device copied to the host while it
+ * built this plan.  0 for host-built and loaded plans and for every device-built plan whose forms were packed on the GPU -- all of them, unless
+ * the device packers of the two-phase streams / column-blocked long rows could not allocate their scratch, or DASP_DEVPACK_FORMS=0 asked for the
+ * host packers.  The bounded column samples of the automatic rules are not counted. */
+long long dasp_plan_csr_fetch_bytes(const dasp_plan_t *plan);
 
 /* switch the cache policy of an uploaded plan (values as dasp_options_t::stream_policy); no re-upload */
 int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);
