@@ -260,6 +260,31 @@ class Plan:
             _lib.check(n)
         return n
 
+    def shared_ids(self):
+        """Shared column ids of twin rows (include/dasp_amd.h dasp_plan_shared_ids), no GPU needed: a dict with `available` (the plan has a shared id
+        plane), `paired_id_bytes` (id bytes streamed for the paired regions without it), `shared_bytes` (plane + table) and `in_use` (the uploaded plan
+        launches the kernel that reads it)."""
+        pb, sb, use = C.c_longlong(0), C.c_longlong(0), C.c_int(0)
+        rc = _lib.lib().dasp_plan_shared_ids(self._h, C.byref(pb), C.byref(sb), C.byref(use))
+        if rc < 0:
+            _lib.check(rc)
+        return {"available": bool(rc), "paired_id_bytes": int(pb.value), "shared_bytes": int(sb.value), "in_use": bool(use.value)}
+
+    def shared_ids_export(self):
+        """(plane, table) of the shared id plane as uint32 arrays; table has one row of four words per medium block: ranks of rows 0-7, ranks of rows 8-15
+        (4 bits each), offset into the plane in units of 16 bytes, number of distinct lists."""
+        out = []
+        for what in (b"plane", b"table"):
+            n = int(_lib.lib().dasp_plan_shared_ids_export(self._h, what, None, 0))
+            if n < 0:
+                _lib.check(n)
+            a = np.empty(n // 4, np.uint32)
+            n2 = int(_lib.lib().dasp_plan_shared_ids_export(self._h, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
+            if n2 < 0:
+                _lib.check(n2)
+            out.append(a)
+        return out[0], out[1].reshape(-1, 4)
+
     @property
     def value_map_slots(self):
         """Mapped value slots over all value arrays (panels included); 0 without a map."""

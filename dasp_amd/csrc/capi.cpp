@@ -311,6 +311,45 @@ static long long host_array_impl(const dasp_plan_t *plan, const char *name, cons
 
 long long dasp_plan_csr_fetch_bytes(const dasp_plan_t *plan) { return plan ? plan->impl.csr_fetch_bytes : (long long)DASP_ERR_ARG; }
 
+int dasp_plan_shared_ids(const dasp_plan_t *plan, long long *paired_id_bytes, long long *shared_bytes, int *in_use)
+{
+    if (!plan) return DASP_ERR_ARG;
+    const Plan &p = plan->impl;
+    if (paired_id_bytes) *paired_id_bytes = 0;
+    if (shared_bytes) *shared_bytes = 0;
+    if (in_use) *in_use = p.dev && p.sh_in_use ? 1 : 0;
+    return guarded("dasp_plan_shared_ids", [&] {
+        long long pb = 0, sb = 0;
+        if (!p.sh_known) {                        // (once: upload, or the first query; a plan whose host arrays were dropped before either has no plane to report)
+            SharedIds sh;
+            (void)derive_shared_ids(p, sh);
+            p.sh_paired_bytes = sh.paired_id_bytes; p.sh_shared_bytes = sh.shared_bytes; p.sh_known = true;
+        }
+        pb = p.sh_paired_bytes; sb = p.sh_shared_bytes;
+        if (pb == 0) return 0;
+        if (paired_id_bytes) *paired_id_bytes = pb;
+        if (shared_bytes) *shared_bytes = sb;
+        return 1;
+    });
+}
+
+long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what, void *dst, size_t bytes)
+{
+    if (!plan || !what) return DASP_ERR_ARG;
+    long long need = 0;
+    const int rc = guarded("dasp_plan_shared_ids_export", [&] {
+        const bool plane = std::strcmp(what, "plane") == 0;
+        if (!plane && std::strcmp(what, "table") != 0) { set_error("dasp_plan_shared_ids_export: \"plane\" or \"table\""); return (int)DASP_ERR_ARG; }
+        SharedIds sh;
+        if (!derive_shared_ids(plan->impl, sh)) { set_error("the plan has no shared id plane (f64 with 16-bit ids, host arrays present, at least one pipelined block)"); return (int)DASP_ERR_STATE; }
+        const std::vector<uint32_t> &v = plane ? sh.plane : sh.table;
+        need = (long long)v.size() * 4;
+        if (dst && bytes >= (size_t)need && need > 0) std::memcpy(dst, v.data(), (size_t)need);
+        return (int)DASP_OK;
+    });
+    return rc != DASP_OK ? (long long)rc : need;
+}
+
 int dasp_plan_upload(dasp_plan_t *plan)
 {
     if (!plan) return DASP_ERR_ARG;

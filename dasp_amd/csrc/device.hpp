@@ -64,6 +64,9 @@ struct DevArgs {
     const int *med_nt;                                     // [blocks] tail steps of every medium block = ceil(tail entries of its first, longest row / entries per step) -- derived from irr_ptr at upload (r6)
     int wg_rot;       // workgroup b of the launch serves virtual workgroup (b + wg_rot) mod grid of the [long | medium | short] ranges (upload_plan: which category is dispatched first)
     int win_tiles;    // short tiles folded into every window workgroup (upload_plan): workgroup w also serves tiles w, w + n_windows, ... ; 0: the short tiles keep workgroups of their own
+    // (r7; last again) shared id plane of the pipelined blocks' paired regions (plan.hpp struct SharedIds): the ids of rows with identical id lists stored once per block;
+    // med_shtab = one 16-byte entry per block {ranks lo, ranks hi, offset into the plane / 16, L}.  Null unless the plan launches dasp_spmv_shared_kernel (DevicePlan::shared_ids), the only kernel that reads them
+    const unsigned char *med_shplane; const unsigned *med_shtab;
 };
 
 // two-phase form (plan.hpp struct TwoPhase): what its two kernels read.  All device pointers into the plan's arena; xs is the stream phase 1
@@ -108,6 +111,9 @@ struct DevicePlan {
     bool seven_waves = false;
     // r6: >= 5 % of the plan's nonzeros sit in narrow long pieces (plan.hpp long_cid16) of a plain plan: launch the builds that read their 16-bit ids (kernels.hip L16)
     bool long16 = false;
+    // r7: the arena holds the shared id plane (DevArgs::med_shplane) and the launch uses the kernel that reads it (kernels.hip dasp_spmv_shared_kernel): f64 plans that stream
+    // from HBM and whose twin rows save >= 3 % of the streamed bytes (upload.cpp shared_ids_rule)
+    bool shared_ids = false;
     int device = -1;
     // column-panel parent: arena = the panels' partial results, panel k at ypart + k * ypart_stride elements
     size_t ypart_stride = 0;
@@ -129,6 +135,7 @@ void value_map_free(DevicePlan *d);    // devpack.hip
 int require_device();                  // upload.cpp: DASP_OK, or DASP_ERR_NO_DEVICE with the error text set
 int upload_plan(Plan &p);
 void choose_long16(Plan &p);           // upload.cpp
+long long shared_ids_net_saving(const Plan &p, const SharedIds &s, bool long16);      // upload.cpp: streamed bytes the shared plane saves (choose rule)
 int sync_dev_args(Plan &p);            // upload.cpp: DevicePlan::dargs = DevicePlan::args (a memcmp when nothing changed; a blocking copy otherwise -- never inside a stream capture: upload and the placement trials leave it in sync)
 int upload_plan_unpacked(Plan &p);     // for the device packers: arena + O(rows) arrays, no placement trials yet
 // kernels.hip: one SpMV of an uploaded plan (asynchronous); what upload.cpp asks the kernels

@@ -61,6 +61,24 @@ __global__ __launch_bounds__(WIN ? 1024 : 256, WIN ? kMinWavesWin : MW ? MW : kM
 #endif
 }
 
+// r7: the one-byte-id f64 build whose pipelined blocks read the ids of their paired regions from the shared id plane (plan.hpp struct SharedIds; DevicePlan::shared_ids).
+// A kernel of its own, not an eighth parameter of dasp_spmv_kernel: every other plan runs exactly the code it ran before
+template <bool NT>
+__global__ __launch_bounds__(256, kMinWavesPlain) void dasp_spmv_shared_kernel(CallArgs c)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+#ifdef DASP_STAMPS
+    Stamps st; st.begin(c.stamp_launch);
+#else
+    Stamps st; st.begin(0);
+#endif
+    const DevArgs a = load_args(c);
+    spmv_body<double, NT, true, false, true, false, false, false, true>(a, lds_raw, blockIdx.x, st);
+#ifdef DASP_STAMPS
+    st.finish(a.wpw);
+#endif
+}
+
 // a column panel with row tiles (Plan::rt_*): the non-windowed kernel + the tiles' workgroup range, dynamic LDS = 4 waves x 64 x rt_max products
 // (f16: held to 72 registers = 7 waves per SIMD like the kernel without tiles -- 75 otherwise; ljournal-2008 0.4522 -> 0.4443 ms)
 template <class T, bool NT, bool C16>
@@ -503,6 +521,9 @@ static int launch_typed(Plan &p, const DevArgs &a, hipStream_t s)
         if (p.windowed && p.dev->win1 && !nt) {                             // at most one window workgroup per CU: the 128-register build
             if (c16) hipLaunchKernelGGL((dasp_spmv_win1_kernel<T, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
             else hipLaunchKernelGGL((dasp_spmv_win1_kernel<T, false>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
+        } else if (sizeof(T) == 8 && c16 && !p.windowed && p.dev->shared_ids) {      // twin rows share their ids (upload.cpp): the one-byte-id build over the shared plane
+            if (nt) hipLaunchKernelGGL((dasp_spmv_shared_kernel<true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
+            else hipLaunchKernelGGL((dasp_spmv_shared_kernel<false>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
         } else if (sizeof(T) == 8 && c16 && !p.windowed && p.cnt_reg8 > 0) {      // plans with one-byte ids: their own instantiation
             if (p.dev->seven_waves) {
                 if (nt) hipLaunchKernelGGL((dasp_spmv_kernel<double, true, true, false, true, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);

@@ -348,10 +348,33 @@ struct Plan {
     // dasp_plan_create_device: bytes of the caller's nnz-sized device arrays (column ids, values, map entries) that were copied to the host while this plan
     // was built -- 0 unless a form took the host packers (DASP_DEVPACK_FORMS=0, or the device packers' scratch did not fit)
     long long csr_fetch_bytes = 0;
+    // what upload found for dasp_plan_shared_ids (struct SharedIds below): the figures of the derived plane, and whether the launch reads it (= DevicePlan::shared_ids)
+    // (sh_known: the two figures are valid -- set by upload or by the first dasp_plan_shared_ids, so that a second query derives nothing; the id planes never change)
+    mutable long long sh_paired_bytes = 0, sh_shared_bytes = 0;
+    mutable bool sh_known = false;
+    bool sh_in_use = false;
     DevicePlan *dev = nullptr;
 
     ~Plan();
 };
+
+// ---- shared id plane (r7; sharedids.cpp).  A mesh matrix with d unknowns per node has d consecutive rows with the same column list, and a medium
+// block is 16 consecutive length-sorted rows: inside the paired region of a PIPELINED block (nc + nt > kMedShot64, med_npair > 0 -- the positions the kernel's load4 reads)
+// the 16 rows' packed id fields fall into L <= 16 distinct lists.  Rows are TWINS when their stored bytes agree at every paired position (one-byte offsets below n8, u16
+// offsets above, pads included); rank[row] = its list in order of first appearance.  The plane stores every list once, in today's layout with L in place of the 16 rows:
+//   narrow batch j (positions 4j .. 4j+3):      [kq][rank] dwords of four one-byte ids    16 L bytes
+//   wide pair p (positions n8 + 2p, n8 + 2p+1): [kq][rank] dwords of two u16 ids          16 L bytes
+// a block's narrow batches first, then its wide pairs; a block starts at a multiple of 16 bytes.  table = four words per block: the sixteen 4-bit ranks (two words, row 0
+// in the low bits), the block's offset into the plane in units of 16 bytes, L.  A lane (row, kq) reads dword kq L + rank[row] of a batch / pair -- the same dword it reads
+// from med_cid8 / med_cid16 today.  Blocks that are not pipelined have an all-zero entry.  Derived from the packed plan, which stays as it is.
+struct SharedIds {
+    std::vector<uint32_t> plane, table;
+    long long paired_id_bytes = 0;      // what the kernel streams from med_cid8 / med_cid16 for the same positions
+    long long shared_bytes = 0;         // plane + table
+    int n_pipelined = 0;
+};
+bool shared_ids_qualify(const Plan &p);                        // f64, 16-bit ids, no windows / panels / two-phase form, host id arrays present
+bool derive_shared_ids(const Plan &p, SharedIds &out);         // false: the plan does not qualify or has no pipelined block (out is empty)
 
 // ---- device-side packing (dasp_plan_create_device): the CSR stays on the GPU; the host keeps doing the O(rows) decisions
 // from the row pointer alone and hands the O(nnz) work to the kernels in devpack.hip through these hooks.

@@ -1,0 +1,71 @@
+// sharedids.cpp -- the shared id plane of a packed plan (plan.hpp struct SharedIds): rows of a pipelined medium block whose packed column-id fields are identical
+// keep ONE copy of them.  Host code without a device: upload.cpp places the result in the arena, capi.cpp answers dasp_plan_shared_ids from it.
+#include <cstring>
+
+#include "plan.hpp"
+
+namespace dasp {
+
+bool shared_ids_qualify(const Plan &p)
+{
+    if (p.precision != 64 || !p.cid16 || p.windowed || p.two_phase || !p.panels.empty() || p.panel || p.host_dropped) return false;
+    const size_t nb = p.med_ptr.empty() ? 0 : p.med_ptr.size() - 1;
+    if (nb == 0 || p.med_c8ptr.size() != nb + 1 || p.irr_ptr.size() < 2) return false;
+    // (a plan packed on the device has no host copy of the id planes)
+    return p.med_cid8.size() == p.cnt_reg8 && p.med_cid16.size() == p.cnt_reg - p.cnt_reg8 && p.cnt_reg > 0;
+}
+
+bool derive_shared_ids(const Plan &p, SharedIds &out)
+{
+    out = SharedIds();
+    if (!shared_ids_qualify(p)) return false;
+    constexpr int CH = 64, K = 4;                 // f64: elements per chunk, tail entries of a row per step
+    const size_t nb = p.med_ptr.size() - 1;
+    out.table.assign(4 * nb, 0u);
+    const unsigned char *c8 = p.med_cid8.data();
+    const unsigned char *c16 = reinterpret_cast<const unsigned char *>(p.med_cid16.data());
+    std::vector<const unsigned char *> slot;      // the block's id dwords, 64 per slot (lane = row + 16 kq): narrow batches, then wide pairs
+    for (size_t b = 0; b < nb; ++b) {
+        const int c0 = p.med_ptr[b], nc = p.med_ptr[b + 1] - c0;
+        const size_t r0 = b * (size_t)kMedRows;
+        const int nt = r0 + 1 < p.irr_ptr.size() ? (p.irr_ptr[r0 + 1] - p.irr_ptr[r0] + K - 1) / K : 0;
+        if (med_oneshot64(nc, nt)) continue;
+        const int npair = med_npair(nc, nt, 8, p.pair_mode);
+        if (npair <= 0) continue;
+        const int q0 = p.med_c8ptr[b], n8 = p.med_c8ptr[b + 1] - q0;
+        slot.clear();
+        for (int i = 0; i < n8; i += kMedBatch64) slot.push_back(c8 + (size_t)(q0 + i) * CH);
+        for (int i = n8; i < npair; i += 2) slot.push_back(c16 + 2 * (size_t)(c0 - q0 - n8 + i) * CH);
+        auto same = [&](int r, int q) {
+            for (const unsigned char *s : slot)
+                for (int kq = 0; kq < 4; ++kq)
+                    if (std::memcmp(s + 4 * (r + 16 * kq), s + 4 * (q + 16 * kq), 4) != 0) return false;
+            return true;
+        };
+        int rep[kMedRows], rank[kMedRows], L = 0;
+        for (int r = 0; r < kMedRows; ++r) {
+            int g = 0;
+            while (g < L && !same(r, rep[g])) ++g;
+            if (g == L) rep[L++] = r;
+            rank[r] = g;
+        }
+        unsigned long long ranks = 0;
+        for (int r = 0; r < kMedRows; ++r) ranks |= (unsigned long long)rank[r] << (4 * r);
+        const size_t at = out.plane.size();        // dwords; a multiple of 4
+        out.plane.resize(at + slot.size() * 4 * (size_t)L);
+        uint32_t *dst = out.plane.data() + at;
+        for (const unsigned char *s : slot)
+            for (int kq = 0; kq < 4; ++kq)
+                for (int g = 0; g < L; ++g) std::memcpy(dst++, s + 4 * (rep[g] + 16 * kq), 4);
+        out.table[4 * b] = (uint32_t)ranks; out.table[4 * b + 1] = (uint32_t)(ranks >> 32);
+        out.table[4 * b + 2] = (uint32_t)(at / 4); out.table[4 * b + 3] = (uint32_t)L;
+        out.paired_id_bytes += (long long)slot.size() * 4 * CH;
+        ++out.n_pipelined;
+        if (at / 4 > 0xFFFFFFFFull) { out = SharedIds(); return false; }      // (64 GiB of ids: the offset no longer fits its word)
+    }
+    if (out.n_pipelined == 0) { out = SharedIds(); return false; }
+    out.shared_bytes = (long long)out.plane.size() * 4 + (long long)out.table.size() * 4;
+    return true;
+}
+
+}  // namespace dasp

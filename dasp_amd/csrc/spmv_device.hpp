@@ -118,7 +118,7 @@ __device__ __forceinline__ DevArgs load_args(const CallArgs &c)
     __builtin_memcpy(&a, w, sizeof a);
 #define DASP_G(f) a.f = ldp(&c.plan->f)
     DASP_G(long_val); DASP_G(long_cid); DASP_G(long_cid16); DASP_G(long_base); DASP_G(piece_c16); DASP_G(piece_ptr); DASP_G(piece_dst); DASP_G(partial); DASP_G(multi_ptr); DASP_G(multi_dst);
-    DASP_G(med_ptr); DASP_G(med_val); DASP_G(med_cid); DASP_G(med_cid16); DASP_G(med_base); DASP_G(med_cid8); DASP_G(med_c8ptr);
+    DASP_G(med_ptr); DASP_G(med_val); DASP_G(med_cid); DASP_G(med_cid16); DASP_G(med_base); DASP_G(med_cid8); DASP_G(med_c8ptr); DASP_G(med_shplane); DASP_G(med_shtab);
     DASP_G(irr_ptr); DASP_G(med_nt); DASP_G(irr_val); DASP_G(irr_cid); DASP_G(med_dst); DASP_G(win_cmin); DASP_G(win_len);
     DASP_G(short_val); DASP_G(short_cid); DASP_G(groups); DASP_G(order);
     DASP_G(rt_val); DASP_G(rt_cid); DASP_G(rt_ptr); DASP_G(rt_start); DASP_G(rt_mask);
@@ -317,7 +317,10 @@ struct PieceSrc {
 // arena pads them) and are zeroed in gather(), so neither stage has a divergent branch.
 // C8: the plan has one-byte ids (f64, 16-bit-id plans with narrow chunks): its own kernel instantiation, so that every other plan runs
 // exactly the code it ran before
-template <class T, bool NT, bool C16, bool PAIRS, bool C8, bool KT = false, bool REL = false>
+// SH (r7, the one-byte-id f64 build only): the paired region's ids come from the shared id plane (plan.hpp struct SharedIds) -- rows of the block with identical id lists
+// read the SAME dword, so a batch touches 16 L instead of 256 bytes of ids.  Only load4's id addresses differ; positions behind the paired region, one-shot blocks and
+// everything after the load are those of the build without it
+template <class T, bool NT, bool C16, bool PAIRS, bool C8, bool KT = false, bool REL = false, bool SH = false>
 struct BlockSrc {
     static constexpr bool kPairs = PAIRS;          // false: the windowed kernel, whose plans keep every chunk lane-linear
     static constexpr int VPL = Tr<T>::CHUNK / kWave;           // values of one chunk per lane: 1 (f64) / 4 (f16)
@@ -333,6 +336,9 @@ struct BlockSrc {
     // plane at the block's first element.  w16 = the u16 plane rebased so that position i's ids sit where the block's own position i
     // would be: w16 = cid16 + e16 - (e0 + n8 * CH), i.e. `w16 + at_of(i)` for i >= n8
     const unsigned char *c8; const unsigned short *w16; int n8;
+    // SH: the block's part of the shared plane -- shn = its first narrow batch, shw = rebased so that position i's wide pair sits at shw + 8 L i (= shn + 4 L n8 +
+    // 8 L (i - n8)); sh4l = 4 L (wave-uniform); shlane4 = 4 (kq L + rank of the lane's row): this lane's dword inside a batch / pair
+    gbyte_p shn, shw; unsigned sh4l, shlane4;
     const T *ival; const int *icid; int t0, t1, kq;
     // element index of this lane's first value (and id) of regular chunk i -- wave-uniform part + lane part
     template <bool PAIRED_OK> __device__ __forceinline__ size_t at_of(int i) const
@@ -394,9 +400,16 @@ struct BlockSrc {
         const f64x2 v1 = ldg<NT>(reinterpret_cast<const f64x2 *>(reg.val + at + 2 * CH));
         f[0].a = v0[0]; f[1].a = v0[1]; f[2].a = v1[0]; f[3].a = v1[1];
         const bool narrow = i + 4 <= n8;                        // wave-uniform
-        const gbyte_p pa = narrow ? (gbyte_p)(c8 + (size_t)i * CH) : (gbyte_p)(w16 + reg.e0 + (size_t)i * CH);
-        const gbyte_p pb = narrow ? pa : pa + 4 * CH;           // the wide batch's second pair: 2 chunks x CH u16 further
-        const unsigned lo4 = 4u * (unsigned)reg.lane;
+        gbyte_p pa, pb; unsigned lo4;
+        if constexpr (SH) {                                     // a narrow batch is 16 L bytes (4 L per position), a wide pair 16 L bytes (8 L per position)
+            pa = narrow ? shn + (size_t)((unsigned)i * sh4l) : shw + (size_t)((unsigned)i * (2u * sh4l));
+            pb = narrow ? pa : pa + 4u * sh4l;
+            lo4 = shlane4;
+        } else {
+            pa = narrow ? (gbyte_p)(c8 + (size_t)i * CH) : (gbyte_p)(w16 + reg.e0 + (size_t)i * CH);
+            pb = narrow ? pa : pa + 4 * CH;           // the wide batch's second pair: 2 chunks x CH u16 further
+            lo4 = 4u * (unsigned)reg.lane;
+        }
         const unsigned ra = ldg<NT>((const __attribute__((address_space(1))) unsigned *)(pa + lo4));
         const unsigned rb = ldg<NT>((const __attribute__((address_space(1))) unsigned *)(pb + lo4));
         f[0].c = (int)ra; f[1].c = (int)ra; f[2].c = (int)rb; f[3].c = (int)rb;
@@ -630,7 +643,7 @@ __device__ __forceinline__ bool diag_of(const f32x4 &acc, int lane, float &d)
 // DASP_Y_NATURAL (a.order set); 2: med_dst[position] (windowed mode)
 // WU / WS (windowed f64 only; 0 = the defaults of Tr<T>): pipeline batch and longest one-shot unit of the build held to 64 registers -- with 4 + 4 fragments in flight it
 // spilled 12-29 VGPRs; windowed plans store no pairs, so their layout does not depend on the batch
-template <class T, bool NT, bool C16, int YM, bool C8 = false, int YS = 0, bool REL = false, int WU = 0, int WS = 0, class XV>
+template <class T, bool NT, bool C16, int YM, bool C8 = false, int YS = 0, bool REL = false, int WU = 0, int WS = 0, bool SH = false, class XV>
 __device__ __forceinline__ void medium_block(const DevArgs &a, int b, int lane, const XV &x)
 {
     using acc_t = typename Tr<T>::acc_t;
@@ -650,7 +663,7 @@ __device__ __forceinline__ void medium_block(const DevArgs &a, int b, int lane, 
     // (r6: from the per-block table, a scalar load beside med_ptr's -- the wave does not wait for the vector load of irr_ptr before it issues its tiles' loads; the multi-GPU
     // step kernels, YS != 0, keep the form they were frozen with)
     const int nt = YS == 0 ? tab<true>(a.med_nt, b) : (__builtin_amdgcn_readfirstlane(t1 - t0) + TK - 1) / TK;
-    BlockSrc<T, NT, C16, YM != 2, C8, KT, REL> src;
+    BlockSrc<T, NT, C16, YM != 2, C8, KT, REL, SH> src;
     if constexpr (REL) src.relb = x.cmin; else src.relb = 0;
     src.reg.val = val; src.reg.cid = a.med_cid; src.reg.e0 = (size_t)c0 * CH; src.reg.lane = lane;
     src.nc = c1 - c0; src.npair = med_npair(c1 - c0, nt, (int)sizeof(T), YM == 2 ? 0 : a.pair_mode); src.cid16 = a.med_cid16; src.base = a.med_base; src.c0 = c0;
@@ -658,6 +671,16 @@ __device__ __forceinline__ void medium_block(const DevArgs &a, int b, int lane, 
     if constexpr (C8 && C16 && sizeof(T) == 8 && YM != 2) {
         const int q0 = tab<true>(a.med_c8ptr, b), q1 = tab<true>(a.med_c8ptr, b + 1);
         src.n8 = q1 - q0; src.c8 = a.med_cid8 + (size_t)q0 * CH; src.w16 = a.med_cid16 - (size_t)q1 * CH;      // e16 - (e0 + n8 CH) = -(q0 + n8) CH
+    }
+    if constexpr (SH) {
+        static_assert(C8 && C16 && sizeof(T) == 8 && YM == 0, "the shared id plane belongs to the one-byte-id f64 build");
+        // the block's table entry: ONE 16-byte scalar load {ranks of rows 0-7, ranks of rows 8-15, offset / 16, L} (all zero for a block that is not pipelined: unused there)
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 e = tab<true>(reinterpret_cast<const u32x4 *>(a.med_shtab), b);
+        const unsigned L = e[3], rw = row < 8 ? e[0] : e[1];
+        src.sh4l = 4u * L; src.shlane4 = 4u * ((unsigned)kq * L + ((rw >> (4u * (unsigned)(row & 7))) & 15u));
+        src.shn = (gbyte_p)a.med_shplane + (size_t)e[2] * 16;
+        src.shw = src.shn - (size_t)((unsigned)src.n8 * src.sh4l);
     }
     src.ival = static_cast<const T *>(a.irr_val); src.icid = a.irr_cid; src.t0 = t0; src.t1 = t1; src.kq = kq;
     // (the windowed f16 kernels, held to 64 registers, keep blocks of up to 2 steps in one shot: 4 spill there; windowed plans store no pairs, so their layout does not depend on it)
@@ -1027,7 +1050,7 @@ constexpr int kMinWavesPlain = DASP_MIN_WAVES, kMinWavesWin = 8;
 #define DASP_WIN64_S 6
 #endif
 // W64: the windowed build held to 64 registers (two window workgroups per CU)
-template <class T, bool NT, bool C16, bool WIN, bool C8, bool RT = false, bool W64 = false, bool L16 = false>
+template <class T, bool NT, bool C16, bool WIN, bool C8, bool RT = false, bool W64 = false, bool L16 = false, bool SH = false>
 __device__ __forceinline__ void spmv_body(const DevArgs &a, char *lds_raw, int wg_index, Stamps &st)
 {
     const int lane = threadIdx.x & 63;
@@ -1056,16 +1079,16 @@ __device__ __forceinline__ void spmv_body(const DevArgs &a, char *lds_raw, int w
                 int lo = a.xcd_blk[0], hi = a.xcd_blk[1];
                 PickPair<1, 9>::run(a.xcd_blk, k, lo, hi);
                 const int b = lo + (m >> 3) * kWavesPerWG + wave;
-                if (b < hi) medium_block<T, NT, C16, 0, C8>(a, b, lane, x);
+                if (b < hi) medium_block<T, NT, C16, 0, C8, 0, false, 0, 0, SH>(a, b, lane, x);
             } else if (sizeof(T) == 8 && !a.med_stride) {
                 // f64: the medium range is never capped (upload_plan), one block per wave -- no loop
                 const int b = m * kWavesPerWG + wave;
-                if (b < a.n_blocks) medium_block<T, NT, C16, 0, C8>(a, b, lane, x);
+                if (b < a.n_blocks) medium_block<T, NT, C16, 0, C8, 0, false, 0, 0, SH>(a, b, lane, x);
             } else {
             // grid-stride over the blocks: wg_med is capped (upload_plan) so the medium range is a persistent set of workgroups
 #pragma unroll 1
             for (int b = m * kWavesPerWG + wave; b < a.n_blocks; b += a.wg_med * kWavesPerWG)
-                medium_block<T, NT, C16, 0, C8>(a, b, lane, x);
+                medium_block<T, NT, C16, 0, C8, 0, false, 0, 0, SH>(a, b, lane, x);
             }
         } else {
             // one window per workgroup.  Workgroups are dealt to the 8 XCDs round-robin, so workgroup m of the range takes window (m % 8) * per_xcd + m / 8: every

@@ -93,17 +93,63 @@ static int upload_long_cb(Plan &p, DevicePlan *d, const LcbOffsets &o)
 }
 
 // DevicePlan::long16 from the pieces' narrow flags (host-built plans: at upload; device-built ones: again once the device packer has sent the flags back)
+static bool long16_rule(const Plan &p, long long *narrow_elems)
+{
+    bool on = false;
+    long long narrow = 0;
+    if (!p.windowed && p.cnt_reg8 == 0 && p.piece_c16.size() == 2 * p.piece_dst.size() && !p.piece_dst.empty()) {
+        for (size_t q = 0; q < p.piece_dst.size(); ++q) if (p.piece_c16[2 * q + 1]) narrow += p.piece_ptr[q + 1] - p.piece_ptr[q];
+        on = narrow * 20 >= (long long)p.nnz && narrow > 0;
+        if (const char *e = std::getenv("DASP_LONG16")) on = std::atoi(e) != 0;      // A/B knob
+    }
+    if (narrow_elems) *narrow_elems = narrow;
+    return on;
+}
 void choose_long16(Plan &p)
 {
     DevicePlan *d = p.dev;
     if (!d) return;
-    d->long16 = false;
-    if (!p.windowed && p.cnt_reg8 == 0 && p.piece_c16.size() == 2 * p.piece_dst.size() && !p.piece_dst.empty()) {
-        long long narrow = 0;
-        for (size_t q = 0; q < p.piece_dst.size(); ++q) if (p.piece_c16[2 * q + 1]) narrow += p.piece_ptr[q + 1] - p.piece_ptr[q];
-        d->long16 = narrow * 20 >= (long long)p.nnz && narrow > 0;
-        if (const char *e = std::getenv("DASP_LONG16")) d->long16 = std::atoi(e) != 0;      // A/B knob
+    d->long16 = long16_rule(p, nullptr);
+}
+
+// r7, the shared id plane (plan.hpp struct SharedIds): streamed bytes per SpMV it saves -- the id bytes of the paired regions minus the plane and its table, minus 2 bytes
+// per element of the narrow long pieces where the plan would otherwise run the build that reads their 16-bit ids (the shared build reads the 32-bit ones)
+long long shared_ids_net_saving(const Plan &p, const SharedIds &s, bool long16)
+{
+    long long narrow = 0;
+    (void)long16_rule(p, &narrow);
+    return s.paired_id_bytes - s.shared_bytes - (long16 ? 2 * narrow : 0);
+}
+// is the shared kernel launched?  The plan streams from HBM (the line of the non-temporal policy) and the plane saves >= 3 % of its streamed bytes; DASP_SHARE_IDS=1 / 0
+// (read at upload) forces it on wherever a plane can be derived / off
+// DevicePlan::seven_waves (device.hpp): most of the regular chunks sit in one-shot blocks of a bandwidth-bound f64 plan
+static bool seven_waves_rule(const Plan &p)
+{
+    bool on = false;
+    if (p.precision == 64 && !p.windowed && p.med_ptr.size() > 1 && p.irr_ptr.size() > 1) {
+        long long one = 0, all = 0;
+        const int K = p.geo.med_k, nbk = (int)p.med_ptr.size() - 1;
+        for (int b = 0; b < nbk; ++b) {
+            const int nc = p.med_ptr[(size_t)b + 1] - p.med_ptr[(size_t)b], r0 = b * kMedRows;
+            const int nt = (p.irr_ptr[(size_t)r0 + 1] - p.irr_ptr[(size_t)r0] + K - 1) / K;
+            all += nc + nt;
+            if (med_oneshot64(nc, nt)) one += nc + nt;
+        }
+        // (bandwidth-bound plans only: webbase-1M f64, 43 MB in 29 us, loses 1.7 % on the 72-register build; nlpkkt160 0.4636 -> 0.4426 ms, x0.1 = 291 MB 41.6 -> 40.7 us)
+        on = all > 0 && one * 10 >= all * 7 && p.stats.data_X > (64ll << 20);
+        if (const char *e = std::getenv("DASP_SEVEN_WAVES")) on = std::atoi(e) != 0;      // A/B knob
     }
+    return on;
+}
+static int share_ids_env() { const char *e = std::getenv("DASP_SHARE_IDS"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }
+static bool shared_ids_rule(const Plan &p, const SharedIds &s)
+{
+    // a plan of one-shot blocks keeps the 7-wave build (seven_waves_rule, DASP_SEVEN_WAVES=1 included): the shared kernel is the 6-wave one-byte-id build, and what it
+    // saves lies in pipelined blocks, which such a plan hardly has
+    if (seven_waves_rule(p)) return false;
+    const int env = share_ids_env();
+    if (env >= 0) return env == 1;
+    return p.stats.data_X > kStreamBytes && shared_ids_net_saving(p, s, long16_rule(p, nullptr)) * 100 >= 3 * p.stats.data_X;
 }
 
 void release_device(Plan &p)
@@ -237,6 +283,20 @@ static int upload_plan_impl(Plan &p)
     std::vector<int> ord_mapped;   // a column panel writes row r to dst_map[r] (its parent's slot), not to r
     if (natural && !p.dst_map.empty()) { ord_mapped.resize(p.order.size()); for (size_t i = 0; i < p.order.size(); ++i) ord_mapped[i] = p.dst_map[(size_t)p.order[i]]; }
     const size_t o_ord = add(natural ? (ord_mapped.empty() ? p.order.data() : ord_mapped.data()) : nullptr, natural ? p.order.size() * 4 : 0);
+    // r7: the shared id plane and its per-block table, derived here from the packed id planes (which stay in the arena: the multi-GPU step kernels, the one-shot blocks, the
+    // positions behind the paired region and dasp_plan_download_array read them) -- behind everything else, so that every other array keeps its offset.  Only plans that can
+    // use it pay for the derivation: those that stream from HBM, or any qualifying plan under DASP_SHARE_IDS=1; and only a plan that launches the shared kernel carries the
+    // plane in its arena (0.26-0.45 of the paired id bytes: 0.29 B per nonzero on HV15R) -- every other plan's arena is byte for byte what it was
+    SharedIds sh;
+    size_t o_shp = 0, o_sht = 0;
+    d->shared_ids = false;
+    p.sh_in_use = false;
+    if (share_ids_env() != 0 && (p.stats.data_X > kStreamBytes || share_ids_env() == 1)) {
+        const bool have = derive_shared_ids(p, sh);
+        p.sh_paired_bytes = sh.paired_id_bytes; p.sh_shared_bytes = sh.shared_bytes; p.sh_known = true;
+        p.sh_in_use = d->shared_ids = have && shared_ids_rule(p, sh);
+        if (d->shared_ids) { o_shp = add(sh.plane.data(), sh.plane.size() * 4); o_sht = add(sh.table.data(), sh.table.size() * 4); }
+    }
 
     HIP_TRY(hipMalloc(&d->arena, total));
     d->arena_bytes = total;
@@ -266,6 +326,7 @@ static int upload_plan_impl(Plan &p)
     a.wg_long = (a.n_pieces + a.wpw - 1) / a.wpw;
     a.med_cid16 = (const unsigned short *)(base + o_mc16); a.med_base = (const int *)(base + o_mb);
     a.med_cid8 = (const unsigned char *)(base + o_mc8); a.med_c8ptr = (const int *)(base + o_c8p);
+    a.med_shplane = d->shared_ids ? (const unsigned char *)(base + o_shp) : nullptr; a.med_shtab = d->shared_ids ? (const unsigned *)(base + o_sht) : nullptr;
     a.med_dst = (const int *)(base + o_mdst); a.win_cmin = (const int *)(base + o_wc); a.win_len = (const int *)(base + o_wl);
     a.n_windows = (int)p.win_len.size(); a.blocks_per_win = p.windowed ? p.row_window / kMedRows : 0;
     a.win_hybrid = p.win_hybrid ? 1 : 0; a.win_rel16 = p.win_rel16 ? 1 : 0; a.pair_mode = p.pair_mode;
@@ -275,19 +336,7 @@ static int upload_plan_impl(Plan &p)
     d->win1 = false;
     d->seven_waves = false;
     choose_long16(p);
-    if (p.precision == 64 && !p.windowed && p.med_ptr.size() > 1 && p.irr_ptr.size() > 1) {
-        long long one = 0, all = 0;
-        const int K = p.geo.med_k, nbk = (int)p.med_ptr.size() - 1;
-        for (int b = 0; b < nbk; ++b) {
-            const int nc = p.med_ptr[(size_t)b + 1] - p.med_ptr[(size_t)b], r0 = b * kMedRows;
-            const int nt = (p.irr_ptr[(size_t)r0 + 1] - p.irr_ptr[(size_t)r0] + K - 1) / K;
-            all += nc + nt;
-            if (med_oneshot64(nc, nt)) one += nc + nt;
-        }
-        // (bandwidth-bound plans only: webbase-1M f64, 43 MB in 29 us, loses 1.7 % on the 72-register build; nlpkkt160 0.4636 -> 0.4426 ms, x0.1 = 291 MB 41.6 -> 40.7 us)
-        d->seven_waves = all > 0 && one * 10 >= all * 7 && p.stats.data_X > (64ll << 20);
-        if (const char *e = std::getenv("DASP_SEVEN_WAVES")) d->seven_waves = std::atoi(e) != 0;      // A/B knob
-    }
+    d->seven_waves = seven_waves_rule(p);
     if (p.windowed) {
         int cus = 256;
         hipDeviceProp_t prop;
@@ -409,6 +458,7 @@ static void rebase_args(DevArgs &a, const char *from, const char *to, size_t byt
     mv(a.med_ptr); mv(a.med_val); mv(a.med_cid); mv(a.med_cid16); mv(a.med_base); mv(a.med_cid8); mv(a.med_c8ptr);
     mv(a.irr_ptr); mv(a.med_nt); mv(a.irr_val); mv(a.irr_cid); mv(a.med_dst); mv(a.win_cmin); mv(a.win_len);
     mv(a.short_val); mv(a.short_cid); mv(a.groups); mv(a.order);
+    mv(a.med_shplane); mv(a.med_shtab);
 }
 
 int tune_placement(Plan &p, int trials, const void *dX, void *dY, double *ms_first, double *ms_kept)

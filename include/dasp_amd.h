@@ -347,6 +347,23 @@ long long dasp_plan_value_map_slots(const dasp_plan_t *plan);
  * host packers.  The bounded column samples of the automatic rules are not counted. */
 long long dasp_plan_csr_fetch_bytes(const dasp_plan_t *plan);
 
+/* Shared column ids of twin rows (f64 plans with 16-bit ids, no x windows, panels or two-phase form, host arrays present).  A mesh matrix with d unknowns
+ * per node has d consecutive rows with one column list; inside the paired region of a pipelined medium block such rows store identical id bytes.  At
+ * upload the library derives a plane that keeps each distinct list of a block once, and plans that stream from HBM and save >= 3 % of their streamed
+ * bytes that way run the kernel that reads it (DASP_SHARE_IDS=1 / 0, read at upload: always where a plane exists / never; plans of one-shot blocks,
+ * which run the 7-wave build, never).  Only such a plan carries the plane in device memory (0.26-0.45 of its paired id bytes; HV15R: 0.29 B per
+ * nonzero); every other plan's device arrays are byte for byte what they were.  The packed plan, its file and the results are unchanged: the same ids
+ * reach the same lanes.
+ * dasp_plan_shared_ids answers without a GPU: *paired_id_bytes = id bytes the kernel streams for the paired regions today, *shared_bytes = plane + per-block
+ * table, *in_use = 1 when the uploaded plan launches the shared kernel.  Returns 1 when the plan has such a plane, 0 when it has none (both sizes 0),
+ * < 0 on error.  Any out pointer may be null. */
+int dasp_plan_shared_ids(const dasp_plan_t *plan, long long *paired_id_bytes, long long *shared_bytes, int *in_use);
+/* copy out the plane (what = "plane": 32-bit words, per block its narrow batches then its wide pairs, [kq][list] inside each) or the table (what = "table":
+ * four 32-bit words per medium block -- the sixteen 4-bit list numbers of its rows, low rows first, in two words; the block's offset into the plane in
+ * units of 16 bytes; its number of lists L; all zero for a block that is not pipelined).  Returns the size in bytes (the copy is made when dst holds at
+ * least that much), < 0 on error. */
+long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what, void *dst, size_t bytes);
+
 /* switch the cache policy of an uploaded plan (values as dasp_options_t::stream_policy); no re-upload */
 int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);
 

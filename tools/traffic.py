@@ -25,7 +25,7 @@ SPMV_KERNELS = ("dasp_spmv_panels_kernel", "dasp_long_reduce_panels_kernel", "da
 
 def spmv_kernel(name):
     """which SpMV kernel a (possibly mangled: rocprofv3 does not demangle the _Float16 instantiations) name is, or None"""
-    if "dasp_spmv_win1_kernel" in name or "dasp_spmv_rt_kernel" in name:      # the 128-register build of the windowed kernel (plans of <= 256 windows) / a column panel with row tiles
+    if "dasp_spmv_win1_kernel" in name or "dasp_spmv_rt_kernel" in name or "dasp_spmv_shared_kernel" in name:      # the 128-register build of the windowed kernel (plans of <= 256 windows) / a column panel with row tiles / the build over the shared id plane
         return "dasp_spmv_kernel"
     for k in SPMV_KERNELS:
         if k in name:
