@@ -87,7 +87,7 @@ class Plan:
     def __init__(self, csrRowPtr, csrColIdx, csrVal, colA, precision=64, threshold=0.75, block_longest=256,
                  y_order=Y_PERMUTED, long_piece=0, host_threads=0, part_bounds=None, part_stride=0, x_window=0, row_window=0, cid16=0, stream_policy=0,
                  col_panels=0, slab_max_len=0, x_window_hybrid=0, piece_min_len=0, chunk_pairs=0, cid8=0, short_seg=0, row_tile_max=0, sort_columns=0,
-                 two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0, value_map=0):
+                 two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0, value_map=0, tp_exact=0):
         L = _lib.lib()
         self.precision = precision
         dt = _dtype(precision)
@@ -103,7 +103,7 @@ class Plan:
         opt.col_panels, opt.slab_max_len, opt.x_window_hybrid, opt.piece_min_len = col_panels, slab_max_len, x_window_hybrid, piece_min_len
         opt.chunk_pairs, opt.cid8, opt.short_seg, opt.row_tile_max, opt.sort_columns = chunk_pairs, cid8, short_seg, row_tile_max, sort_columns
         opt.two_phase, opt.tp_col_block, opt.tp_row_block, opt.long_cb = two_phase, tp_col_block, tp_row_block, long_cb
-        opt.value_map = value_map
+        opt.value_map, opt.tp_exact = value_map, tp_exact
         self._pb = None
         if part_bounds is not None:
             self._pb = np.ascontiguousarray(part_bounds, np.int32)
@@ -119,7 +119,7 @@ class Plan:
     def from_device(cls, d_row_ptr, d_col_idx, d_val, rowA, colA, nnzA, precision=64, threshold=0.75, block_longest=256,
                     y_order=Y_PERMUTED, long_piece=0, part_bounds=None, part_stride=0, x_window=0, row_window=0, cid16=0, col_panels=0, slab_max_len=0,
                     x_window_hybrid=0, piece_min_len=0, chunk_pairs=0, cid8=0, short_seg=0, row_tile_max=0, sort_columns=0, two_phase=0, tp_col_block=0, tp_row_block=0, long_cb=0,
-                    value_map=0):
+                    value_map=0, tp_exact=0):
         """Plan from a CSR that already lives on the GPU (integer device addresses): packed by kernels, comes back uploaded."""
         L = _lib.lib()
         self = cls.__new__(cls)
@@ -131,7 +131,7 @@ class Plan:
         opt.slab_max_len, opt.x_window_hybrid, opt.piece_min_len = slab_max_len, x_window_hybrid, piece_min_len
         opt.chunk_pairs, opt.cid8, opt.short_seg, opt.row_tile_max, opt.sort_columns = chunk_pairs, cid8, short_seg, row_tile_max, sort_columns
         opt.two_phase, opt.tp_col_block, opt.tp_row_block, opt.long_cb = two_phase, tp_col_block, tp_row_block, long_cb
-        opt.value_map = value_map
+        opt.value_map, opt.tp_exact = value_map, tp_exact
         self._pb = None
         if part_bounds is not None:
             self._pb = np.ascontiguousarray(part_bounds, np.int32)
@@ -297,6 +297,16 @@ class Plan:
         """0 auto, 1 plain loads (reference dasp_spmv), 2 non-temporal loads (reference dasp_spmv2 'bypass')."""
         _lib.check(_lib.lib().dasp_plan_set_stream_policy(self._h, int(policy)))
 
+    def set_tp_exact(self, on):
+        """Exact, bit-reproducible phase 2 of a two-phase plan on (1) / off (0) (dasp_plan_set_tp_exact): needs no GPU, takes effect with the next
+        launch; no effect on a plan that is not two-phase."""
+        _lib.check(_lib.lib().dasp_plan_set_tp_exact(self._h, int(on)))
+
+    @property
+    def tp_exact(self):
+        """1 for a two-phase plan in exact mode, else 0."""
+        return int(_lib.lib().dasp_plan_tp_exact(self._h))
+
     def spmv(self, dX, dY, stream=0, accumulate=False):
         """dX, dY: integer device addresses (e.g. torch_tensor.data_ptr()); stream: hipStream_t as int.
         accumulate: y += A x instead of y = A x (dasp_plan_spmv_acc)."""
@@ -350,6 +360,19 @@ def spmv_all(filename, csrValA, csrRowPtrA, csrColIdxA, X_val, rowA, colA, nnzA,
     fn = L.dasp_spmv_all_f64 if precision == 64 else L.dasp_spmv_all_f16
     _lib.check(fn(os.fsencode(filename or ""), _vp(v), _vp(rp), _vp(ci), _vp(x), _vp(y), _vp(order), rowA, colA, nnzA, NUM, threshold, block_longest))
     return y, order
+
+
+def tp_exact_dot(a, x, y0=None):
+    """What the exact two-phase mode stores for a row whose products are a[j] * x[j] (float16 arrays of one length): the exact sum rounded once to f64,
+    then to f32 and f16 -- onto y0 (a float16) in the accumulate form.  Host mirror of the kernel's arithmetic (dasp_tp_exact_dot_f16)."""
+    a = np.ascontiguousarray(a, np.float16)
+    x = np.ascontiguousarray(x, np.float16)
+    if a.shape != x.shape or a.ndim != 1:
+        raise ValueError("tp_exact_dot: two float16 vectors of one length")
+    out = C.c_uint16(0)
+    y_in = int(np.array(0 if y0 is None else y0, np.float16).view(np.uint16))
+    _lib.check(_lib.lib().dasp_tp_exact_dot_f16(_vp(a), _vp(x), a.size, 0 if y0 is None else 1, y_in, C.byref(out)))
+    return np.array(out.value, np.uint16).view(np.float16)[()]
 
 
 def partition_rows(csrRowPtr, n_parts):

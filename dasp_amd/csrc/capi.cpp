@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "plan.hpp"
+#include "tp_exact.hpp"
 
 namespace dasp {
 const char *last_error_cstr();
@@ -102,6 +103,7 @@ static int normalise_options(Plan &p, const dasp_options_t *opt, int colA)
         p.opt.part_bounds = p.part_bounds.data();
     } else { p.opt.n_parts = 0; p.opt.part_bounds = nullptr; }
     if (p.opt.value_map != 0 && p.opt.value_map != 1) { set_error("value_map must be 0 or 1"); return DASP_ERR_ARG; }
+    if (p.opt.tp_exact != 0 && p.opt.tp_exact != 1) { set_error("tp_exact must be 0 or 1"); return DASP_ERR_ARG; }
     return DASP_OK;
 }
 
@@ -120,6 +122,7 @@ int dasp_plan_create(dasp_plan_t **out, int precision, int rowA, int colA, int n
         p.precision = precision; p.m = rowA; p.n = colA; p.nnz = nnzA;
         if (int rc = normalise_options(p, opt, colA)) return rc;
         if (int rc = build_plan(p, rp, ci, val)) return rc;
+        if (int rc = set_tp_exact(p, p.opt.tp_exact)) return rc;      // (a plan that did not come out two-phase ignores it)
         *out = h.release();
         return (int)DASP_OK;
     });
@@ -147,6 +150,7 @@ int dasp_plan_create_device(dasp_plan_t **out, int precision, int rowA, int colA
         if (int rc = normalise_options(p, opt, colA)) return rc;
         const DevCsr dev{dRowPtr, dColIdx, dVal};
         if (int rc = build_plan(p, rp.data(), nullptr, nullptr, &dev)) return rc;
+        if (int rc = set_tp_exact(p, p.opt.tp_exact)) return rc;
         *out = h.release();
         return (int)DASP_OK;
     });
@@ -384,6 +388,23 @@ int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy)
 {
     if (!plan) return DASP_ERR_ARG;
     return set_stream_policy(plan->impl, policy);
+}
+
+int dasp_plan_set_tp_exact(dasp_plan_t *plan, int on)
+{
+    if (!plan) return DASP_ERR_ARG;
+    return guarded("dasp_plan_set_tp_exact", [&] { return set_tp_exact(plan->impl, on); });
+}
+
+int dasp_plan_tp_exact(const dasp_plan_t *plan) { return plan && plan->impl.two_phase && plan->impl.tp_exact ? 1 : 0; }
+
+// the host mirror of dasp_tp_reduce_exact_kernel's arithmetic, from the same header: what exact mode stores for a row of these products
+int dasp_tp_exact_dot_f16(const uint16_t *a, const uint16_t *x, long long n, int accumulate, uint16_t y_in, uint16_t *y_out)
+{
+    if (n < 0 || (n > 0 && (!a || !x)) || !y_out || (accumulate != 0 && accumulate != 1)) { set_error("dasp_tp_exact_dot_f16: bad arguments"); return DASP_ERR_ARG; }
+    if (n >= tpx::kMaxTerms) { set_error("dasp_tp_exact_dot_f16: the exact 64-bit sums hold fewer than 4194304 products"); return DASP_ERR_ARG; }
+    *y_out = tpx::dot_f16(a, x, n, accumulate == 1, y_in);
+    return DASP_OK;
 }
 
 int dasp_plan_spmv(dasp_plan_t *plan, const void *dX, void *dY, void *stream)

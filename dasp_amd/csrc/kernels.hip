@@ -34,6 +34,7 @@
 #include "device.hpp"
 
 #include "spmv_device.hpp"
+#include "tp_exact.hpp"
 
 namespace dasp {
 #ifdef DASP_STAMPS
@@ -330,6 +331,92 @@ __global__ __launch_bounds__(512) void dasp_tp_reduce_kernel(TpDev a, T *__restr
     else for (int i = threadIdx.x; i < rows; i += 512) y[p0 + i] = (T)(float)yl[i];
 }
 
+// Phase 2, exact (Plan::tp_exact, dasp_plan_set_tp_exact; the arithmetic and its bounds: tp_exact.hpp).  Same grid, same three streams, same two collision savers as
+// dasp_tp_reduce_kernel; an output position is TWO 64-bit integers in LDS (the row's sum in units of 2^-8 and of 2^-48: planes H[rows], L[rows]) and 4 flag bits
+// (+inf / -inf / NaN product seen; 8 positions per word behind the planes).  Integer adds and ORs are associative, so the sums do not depend on the order in which the
+// no-return LDS atomics land: y is the exact row sum, rounded once to f64 and from there to f16 -- the same bits in every run and for every block geometry.
+// A lane's run and a segment's run are still combined in f64 registers (exact there: tpx::kMaxPairTerms) and become integers only where they are added to LDS: two
+// ds_add_u64 per run.  Dynamic LDS: rb_max x 16 bytes + (rb_max + 7) / 8 words.
+__global__ __launch_bounds__(512) void dasp_tp_reduce_exact_kernel(TpDev a, _Float16 *__restrict__ y, int acc)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    typedef _Float16 vec8 __attribute__((ext_vector_type(8)));
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const int r = blockIdx.x;
+    const int p0 = a.rb_row0[r], rows = a.rb_row0[r + 1] - p0;
+    unsigned long long *Hs = reinterpret_cast<unsigned long long *>(lds_raw), *Ls = Hs + rows;
+    unsigned *fl = reinterpret_cast<unsigned *>(Ls + rows);
+    for (int i = threadIdx.x; i < 2 * rows; i += 512) Hs[i] = 0ull;
+    for (int i = threadIdx.x; i < (rows + 7) / 8; i += 512) fl[i] = 0u;
+    __syncthreads();
+    const int s0 = a.rb_seg0[r], s1 = a.rb_seg0[r + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int LPS = kTpSeg / 8, SPW = 64 / LPS;
+    const int sub = lane / LPS, off = (lane % LPS) * 8;
+    const _Float16 *val = static_cast<const _Float16 *>(a.val), *xs = static_cast<const _Float16 *>(a.xs);
+    auto flush = [&](unsigned row, tpx::Pair run) {
+        const tpx::Fixed f = tpx::to_fixed(run);
+        __hip_atomic_fetch_add(Hs + row, (unsigned long long)f.H, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(Ls + row, (unsigned long long)f.L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+#pragma unroll 2
+    for (int g = s0 + wave * SPW; g < s1; g += 8 * SPW) {
+        const int seg = g + sub;
+        if (seg < s1) {
+            const size_t at = (size_t)seg * kTpSeg + off;
+            const vec8 v = __builtin_nontemporal_load(reinterpret_cast<const vec8 *>(val + at));
+            const tp_u16x8 lr = __builtin_nontemporal_load(reinterpret_cast<const tp_u16x8 *>(a.lrow + at));
+            const vec8 xv = __builtin_nontemporal_load(reinterpret_cast<const vec8 *>(xs + at));
+            float p[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) p[j] = (float)v[j] * (float)xv[j];
+            // a product is non-finite only where an operand is (tested on the packed bit patterns: rare, and wave-uniformly absent in a finite product): it sets its
+            // flag and leaves the sums; a pad's product (value 0 x whatever x its column block starts with) is dropped either way
+            const u32x4 vb = __builtin_bit_cast(u32x4, v), xb = __builtin_bit_cast(u32x4, xv);
+            if ((tpx::nonfinite_f16x2(vb[0]) | tpx::nonfinite_f16x2(vb[1]) | tpx::nonfinite_f16x2(vb[2]) | tpx::nonfinite_f16x2(vb[3]) |
+                 tpx::nonfinite_f16x2(xb[0]) | tpx::nonfinite_f16x2(xb[1]) | tpx::nonfinite_f16x2(xb[2]) | tpx::nonfinite_f16x2(xb[3])) != 0u) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned f = tpx::flag_of(p[j]);
+                    if (f) {
+                        const unsigned row = lr[j];
+                        if (row != kTpPadRow) __hip_atomic_fetch_or(fl + (row >> 3), f << (4 * (row & 7)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        p[j] = 0.0f;
+                    }
+                }
+            }
+            unsigned cur = lr[0];
+            tpx::Pair run = tpx::split(p[0]);
+            bool one_run = true;
+#pragma unroll
+            for (int j = 1; j < 8; ++j) {
+                const unsigned r = lr[j];
+                const tpx::Pair q = tpx::split(p[j]);
+                if (r == cur) run = tpx::add(run, q);
+                else {
+                    if (cur != kTpPadRow) flush(cur, run);
+                    cur = r; run = q; one_run = false;
+                }
+            }
+            // the segmented scan of dasp_tp_reduce_kernel on the pair: lanes of one segment that each hold one run of the same row (<= 64 products: exact in f64)
+            const unsigned key = one_run && cur != kTpPadRow ? cur : 0x10000u + (unsigned)lane;
+            const int ls = lane % LPS;
+#define DASP_TP_SCAN(D, CTRL) if constexpr (D < LPS) { const unsigned k2 = (unsigned)__builtin_amdgcn_update_dpp((int)key, (int)key, CTRL, 0xf, 0xf, false); const tpx::Pair r2{dpp_mov_f64<CTRL>(run.hi), dpp_mov_f64<CTRL>(run.lo)}; if (ls >= D && k2 == key) run = tpx::add(run, r2); }
+            DASP_TP_SCAN(1, 0x111) DASP_TP_SCAN(2, 0x112) DASP_TP_SCAN(4, 0x114)
+#undef DASP_TP_SCAN
+            const unsigned knext = (unsigned)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x101, 0xf, 0xf, false);       // row_shl:1
+            const bool last = ls == LPS - 1 || knext != key;
+            if (cur != kTpPadRow && last) flush(cur, run);
+        }
+    }
+    __syncthreads();
+    const long long *Hi = reinterpret_cast<const long long *>(Hs), *Li = reinterpret_cast<const long long *>(Ls);
+    for (int i = threadIdx.x; i < rows; i += 512) {
+        const double d = tpx::finish(tpx::Fixed{Hi[i], Li[i]}, (fl[i >> 3] >> (4 * (i & 7))) & 7u);
+        y[p0 + i] = acc ? (_Float16)((float)y[p0 + i] + (float)d) : (_Float16)(float)d;
+    }
+}
+
 // ------------------------------------------------------------------ column-blocked long rows of a column-panel plan (plan.hpp struct LongCB)
 // One workgroup (1024 threads) per unit: the column block's slice of x -> LDS, then one wave per (row, block) piece: value x LDS-x, 16 bytes of values per lane
 // and step, wave sum -> partial[piece].  Pads carry local column 0xFFFF and never touch x.
@@ -567,6 +654,7 @@ int tp_kernels_allow_lds()
 {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_tp_expand_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_tp_reduce_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_tp_reduce_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_lcb_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return DASP_OK;
@@ -628,7 +716,9 @@ int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate
             hipLaunchKernelGGL((dasp_lcb_kernel<_Float16>), dim3(q.n_units), dim3(1024), (size_t)q.cb * 2 + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8, s, q, static_cast<const _Float16 *>(dX));
         if (a.n_units > 0)
             hipLaunchKernelGGL((dasp_tp_expand_kernel<_Float16>), dim3(a.n_units), dim3(512), (size_t)a.cb * 2, s, a, static_cast<const _Float16 *>(dX));
-        if (a.n_rb > 0)
+        if (a.n_rb > 0 && p.tp_exact)      // exact sums (dasp_plan_set_tp_exact): two 64-bit integers and 4 flag bits per output position
+            hipLaunchKernelGGL(dasp_tp_reduce_exact_kernel, dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 16 + (size_t)((a.rb_max + 7) / 8) * 4, s, a, static_cast<_Float16 *>(dY), accumulate ? 1 : 0);
+        else if (a.n_rb > 0)
             hipLaunchKernelGGL((dasp_tp_reduce_kernel<_Float16>), dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 8, s, a, static_cast<_Float16 *>(dY), accumulate ? 1 : 0);
         if (hub) {
             hipLaunchKernelGGL((dasp_lcb_reduce_kernel<_Float16>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, static_cast<_Float16 *>(dY), 1);

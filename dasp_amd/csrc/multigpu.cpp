@@ -357,6 +357,7 @@ int create_impl(dasp_mg_plan &g, const int *rp, const int *ci, const T *val, con
     opt.short_seg = -1;                        // short rows as slabs: the step kernels are compiled without the wave-segmented path (registers)
     opt.two_phase = -1;                        // (the two-phase form has no column remap and no accumulate-into-the-step: DASP kernels only)
     opt.n_parts = 0; opt.part_bounds = nullptr; opt.part_stride = 0;
+    opt.tp_exact = 0;                          // ... nor the exact two-phase mode (a subplan has a column remap: it is never two-phase)
     opt.value_map = 0;                         // subplans never carry a value map (dasp_plan_update_values is a single-plan entry point)
     const int nnz = rp[m];
     if (!g.square) {

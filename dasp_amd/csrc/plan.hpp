@@ -199,6 +199,7 @@ struct TwoPhase {
     raw_vector<char> val;             // [segments * kTpSeg * vbytes] RB-major
     std::vector<uint32_t> map;        // [segments * kTpSeg] value map of val (opt.value_map; Plan::long_map); empty without one
     size_t segments = 0;
+    long long max_row = 0;            // nonzeros of the longest row stored in the streams (not in a plan file: re-counted from lrow at load); what dasp_plan_set_tp_exact checks
     int n_rb() const { return rb_row0.empty() ? 0 : (int)rb_row0.size() - 1; }
     int n_units() const { return (int)(unit.size() / 3); }
 };
@@ -334,6 +335,9 @@ struct Plan {
     // two-phase form (TwoPhase above): the plan then holds order / stats of the whole matrix and the tile streams, nothing else
     bool two_phase = false;
     TwoPhase tp;
+    // phase 2 sums exactly, in 64-bit integers (dasp_tp_reduce_exact_kernel, tp_exact.hpp): a launch-time switch over the same streams (opt.tp_exact,
+    // dasp_plan_set_tp_exact); never set on a plan that is not two-phase, never stored in a plan file
+    bool tp_exact = false;
 
     // value map (opt.value_map = 1): for every stored slot of a value array, 1 + the index of the nonzero of the CALLER's CSR it holds (through
     // the column sort and the panel split), 0 for a pad.  Same element counts as the value arrays; every nonzero appears exactly once over all
@@ -467,6 +471,9 @@ int build_two_phase_device(Plan &p, const int *rp, const DevCsr &d, const unsign
 // value map entry of nonzero j of the CSR the packers read (Plan::map_src)
 inline uint32_t map_entry(const Plan &p, long long j) { return p.map_src ? p.map_src[j] : (uint32_t)(j + 1); }
 bool validate_two_phase(const Plan &p, std::string &why);
+long long tp_longest_row(const TwoPhase &t);      // nonzeros of the longest row of the streams, counted from the host copy of lrow (a loaded plan's TwoPhase::max_row)
+// exact phase 2 on / off (dasp_plan_set_tp_exact): no effect on a plan that is not two-phase; DASP_ERR_ARG for another value or a row of >= 2^22 nonzeros in the streams
+int set_tp_exact(Plan &p, int on);
 
 // column-blocked long rows (longcb.cpp): which rows (in_lcb[row] = 1) a column-panel plan of P panels hands to them (0 rows: none), the packer, the checks
 int decide_long_cb(const Plan &p, const int *rp, int P, std::vector<unsigned char> &in_lcb, int share_den = 4, int per_block = 64);

@@ -96,7 +96,7 @@ long long tp_row_blocks(TwoPhase &t, int m, long long nnz, int rbm, LenOf len_of
     }
     if (m > 0) t.rb_row0.push_back(m);
     long long nnz_here = 0;
-    for (int r = 0; r < m; ++r) nnz_here += len_of(r);
+    for (int r = 0; r < m; ++r) { nnz_here += len_of(r); t.max_row = std::max<long long>(t.max_row, len_of(r)); }
     return nnz_here;
 }
 
@@ -266,6 +266,31 @@ int build_two_phase_device(Plan &p, const int *rp, const DevCsr &d, const unsign
     if (int rc = tp_offsets(t, cnt, n_rb, n_cb, may_decline, nnz_here, off2, off1)) { tiles = DevTiles{}; return rc; }
     tp_units_and_stats(p, off1, n_cb, t_begin);
     lap("offsets, units");
+    return DASP_OK;
+}
+
+long long tp_longest_row(const TwoPhase &t)
+{
+    long long longest = 0;
+    std::vector<long long> cnt;
+    for (int b = 0; b < t.n_rb(); ++b) {
+        cnt.assign((size_t)(t.rb_row0[(size_t)b + 1] - t.rb_row0[(size_t)b]), 0);
+        for (size_t e = (size_t)t.rb_seg0[(size_t)b] * kTpSeg; e < (size_t)t.rb_seg0[(size_t)b + 1] * kTpSeg; ++e)
+            if (t.lrow[e] != kTpPadRow) longest = std::max(longest, ++cnt[t.lrow[e]]);
+    }
+    return longest;
+}
+
+// The exact sums are two 64-bit integers per row, |H| <= 2^40 and |L| <= 2^39 per product (tp_exact.hpp): fewer than 2^22 products cannot overflow them.
+int set_tp_exact(Plan &p, int on)
+{
+    if (on != 0 && on != 1) { set_error("tp_exact must be 0 or 1"); return DASP_ERR_ARG; }
+    if (!p.two_phase) return DASP_OK;          // every other form adds in a fixed order already
+    if (on && p.tp.max_row >= (1ll << 22)) {
+        set_error("tp_exact: a row of the two-phase streams has " + std::to_string(p.tp.max_row) + " nonzeros; the exact 64-bit sums hold fewer than 4194304 per row (long_cb moves such rows out of the streams)");
+        return DASP_ERR_ARG;
+    }
+    p.tp_exact = on == 1; p.opt.tp_exact = on;
     return DASP_OK;
 }
 

@@ -194,9 +194,14 @@ typedef struct dasp_options {
      *       a third of the entries in rows spanning > x/4; hub rows are fine: same-row elements are combined before they reach LDS); 1 = force; -1 = off.
      *       The automatic rule also declines (the matrix keeps its DASP form) when the tiles' padding to whole 64-element segments would store > 3 x the nonzeros
      *       (large, very sparse matrices: few nonzeros per tile) or the tile table would pass 64 M entries.
-     *   DETERMINISM: this is the one form whose results are not bit-reproducible from run to run -- a row's products reach its f64 LDS accumulator through relaxed
-     *   atomics, so their order of addition is not fixed (the f64 sum rounds ~2^-53; the difference shows only where the final rounding to f16 sits on a tie).  Every other
-     *   path (DASP blocks, slabs, panels, column-blocked long rows, the multi-GPU step) adds in a fixed order.  two_phase = -1 is the deterministic choice.
+     *   DETERMINISM: in its default mode this is the one form whose results are not bit-reproducible from run to run -- a row's products reach its f64 LDS accumulator
+     *   through relaxed atomics, so their order of addition is not fixed (the f64 sum rounds ~2^-53; the difference shows only where the final rounding to f16 sits on a
+     *   tie).  Every other path (DASP blocks, slabs, panels, column-blocked long rows, the multi-GPU step) adds in a fixed order.  tp_exact = 1 (below;
+     *   dasp_plan_set_tp_exact switches an existing plan) makes this form reproducible AND exact: same streams, another phase-2 kernel.
+     *   A caller who needs reproducible results should use tp_exact = 1, not two_phase = -1: on all four f16 graph stand-ins the exact form costs 5-12 % over the
+     *   default mode and runs 1.4-2.7 x faster than the two_phase = -1 plan (ljournal-2008 0.175 / 0.184 / 0.418 ms, rmat_2M 0.082 / 0.086 / 0.133, ljournal-2008-uniform
+     *   0.175 / 0.186 / 0.499, powerlaw_1M 0.127 / 0.142 / 0.200: default / exact / two_phase = -1, profiles/r09_tp_exact.md).  two_phase = -1 remains the choice
+     *   where the hub rows of a hybrid plan must be exact too, or a row holds >= 2^22 nonzeros.
      *   tp_col_block: columns per column block (multiple of 8, <= 65536; 0 = 32768); tp_row_block: most output positions per row block (<= 8192; 0 = 4096). */
     int two_phase;
     int tp_col_block, tp_row_block;
@@ -213,6 +218,18 @@ typedef struct dasp_options {
      * of its own once uploaded (HV15R f64: ~1.1 GB).  Plans from dasp_plan_create and dasp_plan_create_device (whose packers write the map on
      * the GPU) alike; the multi-GPU layer never keeps one. */
     int value_map;
+    /* exact, bit-reproducible phase 2 of the two-phase form (no reference counterpart).  An f16 x f16 product is exact in f32 and an integer multiple of 2^-48 below
+     * 2^32; phase 2 then keeps every output position as two 64-bit integers in LDS (the sum in units of 2^-8 and of 2^-48) and adds with integer LDS atomics, whose
+     * result does not depend on their order.  For every row that lives in the two-phase streams:  d = the EXACT row sum rounded once to f64;  dasp_plan_spmv stores
+     * y = (f16)(f32)d (an empty row: +0);  dasp_plan_spmv_acc stores y = (f16)((f32)y_old + (f32)d).  A row with a NaN product (inf x 0 included) or with products of
+     * both infinities gives NaN, a row with infinities of one sign that infinity; the finite products of such a row are ignored.  The result does not depend on the
+     * run, on tp_col_block / tp_row_block, or on whether the host or the device packer built the plan; dasp_tp_exact_dot_f16 computes it on the host.
+     * The hub rows of a hybrid plan (long_cb: the column-blocked long rows) keep their kernels: they add in a fixed order -- reproducible from run to run -- but
+     * are NOT covered by "exact".
+     *   0 = off (default), 1 = a plan that comes out two-phase starts in exact mode; every other value is DASP_ERR_ARG.  Plans that are not two-phase ignore it
+     *   (they are deterministic already).  Packed arrays, order_rid, the stats and every automatic choice are those of the same plan with 0; a plan file does not
+     *   store the mode (a loaded plan starts at 0).  DASP_ERR_ARG when a row of the streams holds >= 2^22 nonzeros (the 64-bit sums could overflow). */
+    int tp_exact;
 } dasp_options_t;
 
 void dasp_options_default(dasp_options_t *opt);
@@ -366,6 +383,16 @@ long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what,
 
 /* switch the cache policy of an uploaded plan (values as dasp_options_t::stream_policy); no re-upload */
 int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);
+
+/* exact phase 2 of a two-phase plan on (1) / off (0): dasp_options_t::tp_exact for a plan that exists -- host-built, device-built or loaded, uploaded or not;
+ * needs no GPU; takes effect with the next launch (do not switch while a capture of this plan's launches is replayed: a captured graph keeps the kernel it
+ * captured).  DASP_OK without effect on a plan that is not two-phase; DASP_ERR_ARG for another value, or when a row of the two-phase streams has >= 2^22 nonzeros. */
+int dasp_plan_set_tp_exact(dasp_plan_t *plan, int on);
+/* 1 for a two-phase plan in exact mode, else 0 */
+int dasp_plan_tp_exact(const dasp_plan_t *plan);
+/* the host mirror of the exact phase 2 (same arithmetic header as the kernel): *y_out = what exact mode stores for a row whose n products are a[j] x[j]
+ * (binary16 bit patterns) -- with accumulate = 1, onto y_in.  n < 2^22.  The definition of the result that tests and callers compare against. */
+int dasp_tp_exact_dot_f16(const uint16_t *a, const uint16_t *x, long long n, int accumulate, uint16_t y_in, uint16_t *y_out);
 
 /* one SpMV, y = A*x, asynchronous on `stream`.  dX: colA values (or the part_stride layout),
  * dY: rowA values, both device pointers of the plan's precision (dX 16-byte aligned when the plan uses x windows).
