@@ -168,6 +168,11 @@ def lib():
         L.dasp_plan_set_tp_exact.argtypes = [vp, C.c_int]
         L.dasp_plan_tp_exact.argtypes = [vp]
         L.dasp_tp_exact_dot_f16.argtypes = [vp, vp, C.c_longlong, C.c_int, C.c_uint16, C.POINTER(C.c_uint16)]
+    if hasattr(L, "dasp_debug_plan_kernel"):         # (likewise; test hooks of kernels.hip, not part of include/dasp_amd.h nor of EXPORTS)
+        L.dasp_debug_spmv_variant.argtypes = [C.c_int, C.c_uint]
+        L.dasp_debug_spmv_variant.restype = C.c_char_p
+        L.dasp_debug_plan_kernel.argtypes = [vp]
+        L.dasp_debug_plan_kernel.restype = C.c_char_p
     L.dasp_plan_spmv.argtypes = [vp, vp, vp, vp]
     L.dasp_plan_spmv_acc.argtypes = [vp, vp, vp, vp]
     L.dasp_plan_time.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]

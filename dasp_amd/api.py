@@ -293,6 +293,14 @@ class Plan:
             _lib.check(n)
         return n
 
+    def kernel_variant(self):
+        """The SpMV kernel a launch of this uploaded plan runs now, in the spelling of tools/isa_report.py (e.g. `dasp_spmv_kernel<double,0,1,0,1,0,0>`);
+        "two_phase" for a two-phase plan, "panels" for a column-panel parent (ask its panels), "none" for a plan without workgroups."""
+        name = _lib.lib().dasp_debug_plan_kernel(self._h)
+        if name is None:
+            raise _lib.DaspError(-22, _lib.lib().dasp_last_error().decode("utf-8", "replace"))
+        return name.decode()
+
     def set_stream_policy(self, policy):
         """0 auto, 1 plain loads (reference dasp_spmv), 2 non-temporal loads (reference dasp_spmv2 'bypass')."""
         _lib.check(_lib.lib().dasp_plan_set_stream_policy(self._h, int(policy)))

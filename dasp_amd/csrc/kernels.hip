@@ -9,11 +9,13 @@
 // The device code they are made of (fragments, block sources, the software pipeline, the three row categories) is spmv_device.hpp;
 // the plan's way onto the device is upload.cpp; the multi-GPU step kernels are mgstep.hip.
 //
-// dasp_spmv_kernel<T, NT, C16, WIN>:
+// dasp_spmv_kernel<T, NT, C16, WIN, C8, MW, L16>:
 //   NT   streamed tiles with non-temporal loads (the reference's ld.global.cs "bypass" kernel) or plain loads
 //   C16  regular medium tiles carry u16 column offsets from a per-chunk base (10 instead of 12 bytes per f64 nonzero)
 //   WIN  windowed mode: one window of rows per 1024-thread workgroup, its span of x staged once in LDS
 //        (dynamic LDS), every gather of the window served from LDS; y through med_dst
+//   C8 / MW / L16 and the shared-id, row-tile and one-window-per-CU kernels: at their definitions below.  Every launchable instantiation is named ONCE, in the host-side table
+// kSpmvVariants; select_spmv_variant (no HIP call) states which one a plan runs; launch, LDS attribute and occupancy query go through the table's rows (tests/test_kernel_table.py)
 // DevArgs::acc turns every store of a row's result into y += (dasp_plan_spmv_acc); a plan split into column panels runs one
 // such launch per panel into a partial buffer and dasp_panel_sum_kernel adds the partials.
 // Rejected variants (XCD-contiguous ranges, persistent f64 grids, nt / sc1 gathers, vector tail loads, ...) are recorded in
@@ -546,35 +548,73 @@ __global__ void selftest_f16_kernel(float *D)
         }                                                                                      \
     } while (0)
 
+// ---- the variant table: every launchable single-plan SpMV instantiation, named once.  name = the spelling tools/isa_report.py reports; bits = what it is built with
+enum : unsigned { kVNt = 1, kVC16 = 2, kVWin = 4, kVC8 = 8, kVSeven = 16, kVL16 = 32, kVShared = 64, kVRt = 128, kVWin1 = 256 };
+template <class Call> struct Variant { const char *name; void (*fn)(Call); int precision; unsigned bits; };
+using SpmvVariant = Variant<CallArgs>;
+#define DASP_NTC16(M, ...) M(__VA_ARGS__, 0, 0) M(__VA_ARGS__, 0, 1) M(__VA_ARGS__, 1, 0) M(__VA_ARGS__, 1, 1)      // the four (NT, C16) builds of a family
+#define DASP_SPMV(TT, TN, WIN, C8, MW, L16, NT, C16) {"dasp_spmv_kernel<" TN "," #NT "," #C16 "," #WIN "," #C8 "," #MW "," #L16 ">", &dasp_spmv_kernel<TT, NT, C16, WIN, C8, MW, L16>, sizeof(TT) * 8, \
+     (NT ? kVNt : 0u) | (C16 ? kVC16 : 0u) | (WIN ? kVWin : 0u) | (C8 ? kVC8 : 0u) | (MW == 7 ? kVSeven : 0u) | (L16 ? kVL16 : 0u)},
+#define DASP_TILES(KERNEL, TT, TN, NT, C16) {#KERNEL "<" TN "," #NT "," #C16 ">", &KERNEL<TT, NT, C16>, sizeof(TT) * 8, (NT ? kVNt : 0u) | (C16 ? kVC16 : 0u) | kVRt},
+#define DASP_WIN1(TT, TN, C16) {"dasp_spmv_win1_kernel<" TN "," #C16 ">", &dasp_spmv_win1_kernel<TT, C16>, sizeof(TT) * 8, (C16 ? kVC16 : 0u) | kVWin1},
+#define DASP_SHARED(NT) {"dasp_spmv_shared_kernel<" #NT ">", &dasp_spmv_shared_kernel<NT>, 64, (NT ? kVNt : 0u) | kVC16 | kVC8 | kVShared},
+static const SpmvVariant kSpmvVariants[] = {
+    //                                     WIN C8 MW L16
+    DASP_NTC16(DASP_SPMV, double, "double", 0, 0, 0, 0) DASP_NTC16(DASP_SPMV, _Float16, "half", 0, 0, 0, 0)      // the plain builds
+    DASP_NTC16(DASP_SPMV, double, "double", 1, 0, 0, 0) DASP_NTC16(DASP_SPMV, _Float16, "half", 1, 0, 0, 0)      // x windows
+    DASP_SPMV(double, "double", 0, 1, 0, 0, 0, 1) DASP_SPMV(double, "double", 0, 1, 0, 0, 1, 1)                  // one-byte ids (f64 with 16-bit ids): plain and non-temporal loads
+    DASP_SPMV(double, "double", 0, 1, 7, 0, 0, 1) DASP_SPMV(double, "double", 0, 1, 7, 0, 1, 1)                  // ... held to 7 waves per SIMD
+    DASP_NTC16(DASP_SPMV, double, "double", 0, 0, 7, 0)                                                          // 7 waves per SIMD (f64)
+    DASP_NTC16(DASP_SPMV, double, "double", 0, 0, 0, 1) DASP_NTC16(DASP_SPMV, _Float16, "half", 0, 0, 0, 1)      // the 16-bit ids of narrow long pieces
+    DASP_SHARED(0) DASP_SHARED(1) DASP_NTC16(DASP_TILES, dasp_spmv_rt_kernel, double, "double") DASP_NTC16(DASP_TILES, dasp_spmv_rt_kernel, _Float16, "half")
+    DASP_WIN1(double, "double", 0) DASP_WIN1(double, "double", 1) DASP_WIN1(_Float16, "half", 0) DASP_WIN1(_Float16, "half", 1)
+};
+static const Variant<PanelCall> kPanelVariants[] = {DASP_NTC16(DASP_TILES, dasp_spmv_panels_kernel, double, "double") DASP_NTC16(DASP_TILES, dasp_spmv_panels_kernel, _Float16, "half")};      // launch_panels_merged
+#undef DASP_SHARED
+#undef DASP_WIN1
+#undef DASP_TILES
+#undef DASP_SPMV
+#undef DASP_NTC16
+template <class V, size_t N>
+static const V &find_variant(const V (&table)[N], int precision, unsigned bits)      // the row built with exactly `bits`
+{
+    for (const V &v : table) if (v.precision == precision && v.bits == bits) return v;
+    std::abort();          // (every combination select_spmv_variant asks for has a row: tests/test_kernel_table.py walks all keys)
+}
+// ---- which kernel a plan runs: pure host logic, no HIP call.  The first rung that matches wins
+struct VariantKey { int precision; bool nt, c16, windowed, win1, shared_ids, has_reg8, seven_waves, long16, row_tiles; };
+const SpmvVariant &select_spmv_variant(const VariantKey &k)
+{
+    const bool f64 = k.precision == 64, plain = !k.windowed;
+    unsigned bits = (k.nt ? kVNt : 0u) | (k.c16 ? kVC16 : 0u);
+    if (k.row_tiles) bits |= kVRt;                                              // a column panel with row tiles (never windowed, never with one-byte ids: plan.cpp build_panels)
+    else if (k.windowed && k.win1 && !k.nt) bits |= kVWin1;                     // at most one window workgroup per CU: the 128-register build
+    else if (f64 && k.c16 && plain && k.shared_ids) bits |= kVC8 | kVShared;    // twin rows share their ids (upload.cpp): the one-byte-id build over the shared plane
+    else if (f64 && k.c16 && plain && k.has_reg8) bits |= kVC8 | (k.seven_waves ? kVSeven : 0u);      // plans with one-byte ids: their own instantiation
+    else if (plain && k.long16 && !(f64 && k.seven_waves)) bits |= kVL16;       // narrow long pieces that matter: the builds that read their 16-bit ids
+    else if (f64 && plain && k.seven_waves) bits |= kVSeven;
+    else if (k.windowed) bits |= kVWin;
+    return find_variant(kSpmvVariants, f64 ? 64 : 16, bits);
+}
+static VariantKey variant_key(const Plan &p, const DevicePlan &d) { return {p.precision, d.nt, p.cid16, p.windowed, d.win1, d.shared_ids, p.cnt_reg8 > 0, d.seven_waves, d.long16, d.args.wg_rt > 0}; }
 
 // ---- what upload.cpp needs to know about the kernels (it is host code and never names a kernel itself)
 // windowed plans with more than the default 64 KiB of dynamic LDS: the limit must be raised per kernel.  Done at upload (for both
-// cache-policy variants), not in the launch path, so that dasp_plan_spmv stays free of anything a stream capture would reject; the
-// attribute belongs to the kernel, not to the plan: always the device maximum, or a later plan with narrower windows would lower
-// the limit under an earlier one with wider windows
+// cache-policy variants and the one-window-per-CU build), not in the launch path, so that dasp_plan_spmv stays free of anything a stream
+// capture would reject; the attribute belongs to the kernel, not to the plan: always the device maximum, or a later plan with narrower
+// windows would lower the limit under an earlier one with wider windows
 int spmv_kernel_allow_full_lds(int precision, bool c16)
 {
-    const int bytes = kWinLdsMax;          // + the window kernels' static LDS (the unit counter) = under the 160 KiB of a CU
-    hipError_t e1, e2;
-#define DASP_ATTR(TT, NTV, CV) hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_spmv_kernel<TT, NTV, CV, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-    if (precision == 64) { e1 = c16 ? DASP_ATTR(double, true, true) : DASP_ATTR(double, true, false); e2 = c16 ? DASP_ATTR(double, false, true) : DASP_ATTR(double, false, false); }
-    else { e1 = c16 ? DASP_ATTR(_Float16, true, true) : DASP_ATTR(_Float16, true, false); e2 = c16 ? DASP_ATTR(_Float16, false, true) : DASP_ATTR(_Float16, false, false); }
-#undef DASP_ATTR
-    HIP_TRY(e1);
-    HIP_TRY(e2);
-    if (precision == 64) HIP_TRY(c16 ? hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_spmv_win1_kernel<double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-                                     : hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_spmv_win1_kernel<double, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    else HIP_TRY(c16 ? hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_spmv_win1_kernel<_Float16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-                     : hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_spmv_win1_kernel<_Float16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    for (const SpmvVariant &v : kSpmvVariants)
+        if (v.precision == (precision == 64 ? 64 : 16) && ((v.bits & kVC16) != 0) == c16 && (v.bits & (kVWin | kVWin1)))
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(v.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kWinLdsMax));      // + the window kernels' static LDS (the unit counter) = under the 160 KiB of a CU
     return DASP_OK;
 }
 // workgroups of the non-windowed f16 kernel one CU holds at a time (0: unknown)
 int spmv_kernel_f16_resident(bool c16)
 {
-    const void *fn = c16 ? reinterpret_cast<const void *>(&dasp_spmv_kernel<_Float16, true, true, false>)
-                         : reinterpret_cast<const void *>(&dasp_spmv_kernel<_Float16, true, false, false>);
     int fit = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, fn, kWave * kWavesPerWG, 0) != hipSuccess) fit = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, reinterpret_cast<const void *>(find_variant(kSpmvVariants, 16, kVNt | (c16 ? kVC16 : 0u)).fn), kWave * kWavesPerWG, 0) != hipSuccess) fit = 0;
     (void)hipGetLastError();
     return fit;
 }
@@ -583,58 +623,17 @@ template <class T>
 static int launch_typed(Plan &p, const DevArgs &a, hipStream_t s)
 {
     const int grid = a.wg_long + a.wg_med + a.wg_short + a.wg_rt;
-    const bool nt = p.dev->nt;
     if (int rc = sync_dev_args(p)) return rc;          // (a memcmp: the device copy follows DevicePlan::args)
+    CallArgs c{static_cast<const DevArgs *>(p.dev->dargs), a.x, a.y, a.acc, a.ywt};
 #ifdef DASP_STAMPS
-    const CallArgs c{static_cast<const DevArgs *>(p.dev->dargs), a.x, a.y, a.acc, a.ywt, g_stamp_launch >= 0 ? g_stamp_launch++ : -1};
-#else
-    const CallArgs c{static_cast<const DevArgs *>(p.dev->dargs), a.x, a.y, a.acc, a.ywt};
+    c.stamp_launch = g_stamp_launch >= 0 ? g_stamp_launch++ : -1;
 #endif
-    if (a.wg_rt > 0) {      // a column panel with row tiles (never windowed, never with one-byte ids: plan.cpp build_panels)
-        const size_t lds = (size_t)kWavesPerWG * kRowTile * (size_t)a.rt_max * sizeof(typename Tr<T>::part_t);
-        if (nt && p.cid16) hipLaunchKernelGGL((dasp_spmv_rt_kernel<T, true, true>), dim3(grid), dim3(256), lds, s, c);
-        else if (nt) hipLaunchKernelGGL((dasp_spmv_rt_kernel<T, true, false>), dim3(grid), dim3(256), lds, s, c);
-        else if (p.cid16) hipLaunchKernelGGL((dasp_spmv_rt_kernel<T, false, true>), dim3(grid), dim3(256), lds, s, c);
-        else hipLaunchKernelGGL((dasp_spmv_rt_kernel<T, false, false>), dim3(grid), dim3(256), lds, s, c);
-    } else if (grid > 0) {
-        const size_t lds = p.windowed ? (size_t)p.lds_bytes : 0;
-        const bool c16 = p.cid16;
-#define DASP_FOR_EACH(M) \
-        if (nt && c16 && p.windowed) { M(true, true, true); } else if (nt && c16) { M(true, true, false); } \
-        else if (nt && p.windowed) { M(true, false, true); } else if (nt) { M(true, false, false); } \
-        else if (c16 && p.windowed) { M(false, true, true); } else if (c16) { M(false, true, false); } \
-        else if (p.windowed) { M(false, false, true); } else { M(false, false, false); }
-#define DASP_LAUNCH(NTV, CV, WINV) hipLaunchKernelGGL((dasp_spmv_kernel<T, NTV, CV, WINV>), dim3(grid), dim3(kWave * a.wpw), lds, s, c)
-        if (p.windowed && p.dev->win1 && !nt) {                             // at most one window workgroup per CU: the 128-register build
-            if (c16) hipLaunchKernelGGL((dasp_spmv_win1_kernel<T, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else hipLaunchKernelGGL((dasp_spmv_win1_kernel<T, false>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-        } else if (sizeof(T) == 8 && c16 && !p.windowed && p.dev->shared_ids) {      // twin rows share their ids (upload.cpp): the one-byte-id build over the shared plane
-            if (nt) hipLaunchKernelGGL((dasp_spmv_shared_kernel<true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else hipLaunchKernelGGL((dasp_spmv_shared_kernel<false>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-        } else if (sizeof(T) == 8 && c16 && !p.windowed && p.cnt_reg8 > 0) {      // plans with one-byte ids: their own instantiation
-            if (p.dev->seven_waves) {
-                if (nt) hipLaunchKernelGGL((dasp_spmv_kernel<double, true, true, false, true, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-                else hipLaunchKernelGGL((dasp_spmv_kernel<double, false, true, false, true, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            }
-            else if (nt) hipLaunchKernelGGL((dasp_spmv_kernel<double, true, true, false, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else hipLaunchKernelGGL((dasp_spmv_kernel<double, false, true, false, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-        } else if (!p.windowed && p.dev->long16 && !(sizeof(T) == 8 && p.dev->seven_waves)) {      // narrow long pieces that matter: the builds that read their 16-bit ids
-            if (nt && c16) hipLaunchKernelGGL((dasp_spmv_kernel<T, true, true, false, false, 0, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else if (nt) hipLaunchKernelGGL((dasp_spmv_kernel<T, true, false, false, false, 0, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else if (c16) hipLaunchKernelGGL((dasp_spmv_kernel<T, false, true, false, false, 0, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else hipLaunchKernelGGL((dasp_spmv_kernel<T, false, false, false, false, 0, true>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-        } else if (sizeof(T) == 8 && !p.windowed && p.dev->seven_waves) {
-            if (nt && c16) hipLaunchKernelGGL((dasp_spmv_kernel<double, true, true, false, false, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else if (nt) hipLaunchKernelGGL((dasp_spmv_kernel<double, true, false, false, false, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else if (c16) hipLaunchKernelGGL((dasp_spmv_kernel<double, false, true, false, false, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-            else hipLaunchKernelGGL((dasp_spmv_kernel<double, false, false, false, false, 7>), dim3(grid), dim3(kWave * a.wpw), lds, s, c);
-        } else
-        DASP_FOR_EACH(DASP_LAUNCH)
-#undef DASP_LAUNCH
-#undef DASP_FOR_EACH
+    if (grid > 0) {
+        const VariantKey k = variant_key(p, *p.dev);
+        const size_t lds = k.row_tiles ? (size_t)kWavesPerWG * kRowTile * (size_t)a.rt_max * sizeof(typename Tr<T>::part_t) : p.windowed ? (size_t)p.lds_bytes : 0;      // row tiles: 4 waves x 64 x rt_max products
+        hipLaunchKernelGGL(select_spmv_variant(k).fn, dim3(grid), dim3(k.row_tiles ? 256 : kWave * a.wpw), lds, s, c);
     }
-    if (a.n_multi > 0)
-        hipLaunchKernelGGL((dasp_long_reduce_kernel<T>), dim3(a.n_multi), dim3(256), 0, s, c);
+    if (a.n_multi > 0) hipLaunchKernelGGL((dasp_long_reduce_kernel<T>), dim3(a.n_multi), dim3(256), 0, s, c);
     HIP_TRY(hipGetLastError());
     return DASP_OK;
 }
@@ -652,22 +651,23 @@ int set_stream_policy(Plan &p, int policy)
 
 int tp_kernels_allow_lds()
 {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_tp_expand_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_tp_reduce_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_tp_reduce_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&dasp_lcb_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const void *fn : {reinterpret_cast<const void *>(&dasp_tp_expand_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_tp_reduce_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_tp_reduce_exact_kernel),
+                           reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_lcb_kernel<double>)})
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return DASP_OK;
 }
 
 // the panels of a column-panel plan in one launch (+ one stage-2 launch when some panel cut a long row).  DASP_OK, an error, or 1 when the panels
 // cannot share one instantiation of the kernel (windows, one-byte ids, mixed id widths, more than kMaxMergedPanels) or DASP_PANELS_MERGED=0 asks for the old form
 template <class T>
-static int launch_panels_merged_typed(Plan &p, const void *dX, char *part, size_t stride_bytes, hipStream_t s)
+static int launch_panels_merged(Plan &p, const void *dX, char *part, size_t stride_bytes, hipStream_t s)
 {
+    static const bool off = [] { const char *e = std::getenv("DASP_PANELS_MERGED"); return e && std::atoi(e) == 0; }();      // A/B knob
+    if (off || p.panels.size() > (size_t)kMaxMergedPanels) return 1;
     const int np = (int)p.panels.size();
-    PanelCall c{}, r{};
+    PanelCall c{};
     c.x = dX; c.part = part; c.stride_bytes = stride_bytes; c.np = np;
+    PanelCall r = c;
     int grid = 0, grid2 = 0, rt_max = 0;
     const Plan &p0 = p.panels[0]->impl;
     for (int k = 0; k < np; ++k) {
@@ -681,24 +681,44 @@ static int launch_panels_merged_typed(Plan &p, const void *dX, char *part, size_
         c.plan[k] = static_cast<const DevArgs *>(q.dev->dargs); c.wg_end[k] = grid;
         r.plan[k] = c.plan[k]; r.wg_end[k] = grid2;
     }
-    r.x = dX; r.part = part; r.stride_bytes = stride_bytes; r.np = np;
     const size_t lds = (size_t)kWavesPerWG * kRowTile * (size_t)rt_max * sizeof(typename Tr<T>::part_t);
     const bool nt = p0.dev->nt, c16 = p0.cid16;
-    if (grid > 0) {
-        if (nt && c16) hipLaunchKernelGGL((dasp_spmv_panels_kernel<T, true, true>), dim3(grid), dim3(256), lds, s, c);
-        else if (nt) hipLaunchKernelGGL((dasp_spmv_panels_kernel<T, true, false>), dim3(grid), dim3(256), lds, s, c);
-        else if (c16) hipLaunchKernelGGL((dasp_spmv_panels_kernel<T, false, true>), dim3(grid), dim3(256), lds, s, c);
-        else hipLaunchKernelGGL((dasp_spmv_panels_kernel<T, false, false>), dim3(grid), dim3(256), lds, s, c);
-    }
+    if (grid > 0) hipLaunchKernelGGL(find_variant(kPanelVariants, (int)sizeof(T) * 8, (nt ? kVNt : 0u) | (c16 ? kVC16 : 0u) | kVRt).fn, dim3(grid), dim3(256), lds, s, c);
     if (grid2 > 0) hipLaunchKernelGGL((dasp_long_reduce_panels_kernel<T>), dim3(grid2), dim3(256), 0, s, r);
     HIP_TRY(hipGetLastError());
     return DASP_OK;
 }
-static int launch_panels_merged(Plan &p, const void *dX, char *part, size_t stride_bytes, hipStream_t s)
+
+// the column-blocked long rows (Plan::lcb): the streaming kernel's dynamic LDS = the block's slice of x + 16 + one sum per step and piece of a unit
+template <class T>
+static size_t lcb_lds_bytes(const LcbDev &q) { return (size_t)q.cb * sizeof(T) + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8; }
+// a column-panel parent: the panels' products into their partial results, the hub rows, then y = (y +) the sum of the partial results
+template <class T>
+static int launch_panels(Plan &p, const void *dX, void *dY, void *stream, bool accumulate)
 {
-    static const bool off = [] { const char *e = std::getenv("DASP_PANELS_MERGED"); return e && std::atoi(e) == 0; }();      // A/B knob
-    if (off || p.panels.empty() || p.panels.size() > (size_t)kMaxMergedPanels) return 1;
-    return p.precision == 64 ? launch_panels_merged_typed<double>(p, dX, part, stride_bytes, s) : launch_panels_merged_typed<_Float16>(p, dX, part, stride_bytes, s);
+    const size_t stride = p.dev->ypart_stride;
+    T *part = static_cast<T *>(p.dev->arena);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = launch_panels_merged<T>(p, dX, reinterpret_cast<char *>(part), stride * sizeof(T), s)) {
+        if (rc != 1) return rc;          // 1: the panels do not share one kernel instantiation -- one launch (+ stage 2) per panel, as before r5
+        for (size_t k = 0; k < p.panels.size(); ++k)
+            if (int rc2 = launch_spmv(p.panels[k]->impl, dX, part + k * stride, stream, false)) return rc2;
+    }
+    // the hub rows (Plan::lcb): column blocks of x staged in LDS, their result into panel 0's slots of the partial buffer -- BEHIND the panels' launch on the same
+    // stream: a panel's row tiles store 0 at the positions of rows that are empty in it, the hub rows' too.  (r6, measured and not kept: the two hub kernels on a
+    // stream of the plan's own beside the panels, fork / join by events -- powerlaw_1M f64 375 -> 380 us in back-to-back launches, 369 when captured in a graph;
+    // both kernels are bound by what ONE CU keeps in flight, so CUs given to one are taken from the other: profiles/r06_hub_rows.md)
+    if (p.lcb.n_rows() > 0) {
+        const LcbDev &q = p.dev->lcb;
+        hipLaunchKernelGGL((dasp_lcb_kernel<T>), dim3(q.n_units), dim3(1024), lcb_lds_bytes<T>(q), s, q, static_cast<const T *>(dX));
+        hipLaunchKernelGGL((dasp_lcb_reduce_kernel<T>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, part, 0);
+    }
+    constexpr int V = 16 / (int)sizeof(T);      // 16 bytes per thread where y is aligned for them
+    const int np = (int)p.panels.size(), m = p.m, acc = accumulate ? 1 : 0;
+    if (m > 0 && (reinterpret_cast<uintptr_t>(dY) & 15) == 0) hipLaunchKernelGGL((dasp_panel_sum_kernel<T, V>), dim3((m + 256 * V - 1) / (256 * V)), dim3(256), 0, s, part, stride, np, static_cast<T *>(dY), m, acc);
+    else if (m > 0) hipLaunchKernelGGL((dasp_panel_sum_kernel<T, 1>), dim3((m + 255) / 256), dim3(256), 0, s, part, stride, np, static_cast<T *>(dY), m, acc);
+    HIP_TRY(hipGetLastError());
+    return DASP_OK;
 }
 
 int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate)
@@ -712,58 +732,18 @@ int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate
         // per-row sums added into y
         const bool hub = p.lcb.n_rows() > 0;
         const LcbDev &q = p.dev->lcb;
-        if (hub)
-            hipLaunchKernelGGL((dasp_lcb_kernel<_Float16>), dim3(q.n_units), dim3(1024), (size_t)q.cb * 2 + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8, s, q, static_cast<const _Float16 *>(dX));
+        if (hub) hipLaunchKernelGGL((dasp_lcb_kernel<_Float16>), dim3(q.n_units), dim3(1024), lcb_lds_bytes<_Float16>(q), s, q, static_cast<const _Float16 *>(dX));
         if (a.n_units > 0)
             hipLaunchKernelGGL((dasp_tp_expand_kernel<_Float16>), dim3(a.n_units), dim3(512), (size_t)a.cb * 2, s, a, static_cast<const _Float16 *>(dX));
         if (a.n_rb > 0 && p.tp_exact)      // exact sums (dasp_plan_set_tp_exact): two 64-bit integers and 4 flag bits per output position
             hipLaunchKernelGGL(dasp_tp_reduce_exact_kernel, dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 16 + (size_t)((a.rb_max + 7) / 8) * 4, s, a, static_cast<_Float16 *>(dY), accumulate ? 1 : 0);
         else if (a.n_rb > 0)
             hipLaunchKernelGGL((dasp_tp_reduce_kernel<_Float16>), dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 8, s, a, static_cast<_Float16 *>(dY), accumulate ? 1 : 0);
-        if (hub) {
-            hipLaunchKernelGGL((dasp_lcb_reduce_kernel<_Float16>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, static_cast<_Float16 *>(dY), 1);
-        }
+        if (hub) hipLaunchKernelGGL((dasp_lcb_reduce_kernel<_Float16>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, static_cast<_Float16 *>(dY), 1);
         HIP_TRY(hipGetLastError());
         return DASP_OK;
     }
-    if (!p.panels.empty()) {
-        const size_t vb = (size_t)p.geo.vbytes, stride = p.dev->ypart_stride;
-        char *part = static_cast<char *>(p.dev->arena);
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        // the hub rows (Plan::lcb): column blocks of x staged in LDS, their result into panel 0's slots of the partial buffer -- BEHIND the panels' launch on the same
-        // stream: a panel's row tiles store 0 at the positions of rows that are empty in it, the hub rows' too.  (r6, measured and not kept: the two hub kernels on a
-        // stream of the plan's own beside the panels, fork / join by events -- powerlaw_1M f64 375 -> 380 us in back-to-back launches, 369 when captured in a graph;
-        // both kernels are bound by what ONE CU keeps in flight, so CUs given to one are taken from the other: profiles/r06_hub_rows.md)
-        auto launch_hub = [&]() {
-            const LcbDev &q = p.dev->lcb;
-            if (p.precision == 64) {
-                hipLaunchKernelGGL((dasp_lcb_kernel<double>), dim3(q.n_units), dim3(1024), (size_t)q.cb * 8 + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8, s, q, static_cast<const double *>(dX));
-                hipLaunchKernelGGL((dasp_lcb_reduce_kernel<double>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, reinterpret_cast<double *>(part), 0);
-            } else {
-                hipLaunchKernelGGL((dasp_lcb_kernel<_Float16>), dim3(q.n_units), dim3(1024), (size_t)q.cb * 2 + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8, s, q, static_cast<const _Float16 *>(dX));
-                hipLaunchKernelGGL((dasp_lcb_reduce_kernel<_Float16>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, reinterpret_cast<_Float16 *>(part), 0);
-            }
-        };
-        if (int rc = launch_panels_merged(p, dX, part, stride * vb, s)) {
-            if (rc != 1) return rc;          // 1: the panels do not share one kernel instantiation -- one launch (+ stage 2) per panel, as before r5
-            for (size_t k = 0; k < p.panels.size(); ++k)
-                if (int rc2 = launch_spmv(p.panels[k]->impl, dX, part + k * stride * vb, stream, false)) return rc2;
-        }
-        if (p.lcb.n_rows() > 0) launch_hub();
-        const int np = (int)p.panels.size(), m = p.m;
-        const bool wide = (reinterpret_cast<uintptr_t>(dY) & 15) == 0;
-        if (m > 0) {
-            if (p.precision == 64) {
-                if (wide) hipLaunchKernelGGL((dasp_panel_sum_kernel<double, 2>), dim3((m + 511) / 512), dim3(256), 0, s, (const double *)part, stride, np, (double *)dY, m, accumulate ? 1 : 0);
-                else hipLaunchKernelGGL((dasp_panel_sum_kernel<double, 1>), dim3((m + 255) / 256), dim3(256), 0, s, (const double *)part, stride, np, (double *)dY, m, accumulate ? 1 : 0);
-            } else {
-                if (wide) hipLaunchKernelGGL((dasp_panel_sum_kernel<_Float16, 8>), dim3((m + 2047) / 2048), dim3(256), 0, s, (const _Float16 *)part, stride, np, (_Float16 *)dY, m, accumulate ? 1 : 0);
-                else hipLaunchKernelGGL((dasp_panel_sum_kernel<_Float16, 1>), dim3((m + 255) / 256), dim3(256), 0, s, (const _Float16 *)part, stride, np, (_Float16 *)dY, m, accumulate ? 1 : 0);
-            }
-        }
-        HIP_TRY(hipGetLastError());
-        return DASP_OK;
-    }
+    if (!p.panels.empty()) return p.precision == 64 ? launch_panels<double>(p, dX, dY, stream, accumulate) : launch_panels<_Float16>(p, dX, dY, stream, accumulate);
     if (p.windowed && (reinterpret_cast<uintptr_t>(dX) & 15)) {   // the window copy uses 16-byte loads from x + cmin (cmin is 16-byte granular)
         set_error("dX must be 16-byte aligned for a plan with LDS-staged x windows"); return DASP_ERR_ARG;
     }
@@ -775,6 +755,24 @@ int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate
     hipStream_t s = static_cast<hipStream_t>(stream);
     return p.precision == 64 ? launch_typed<double>(p, a, s) : launch_typed<_Float16>(p, a, s);
 }
+
+}  // namespace dasp
+// ---- which kernel?  Test hooks like dasp_debug_set_stamps: exported, not in include/dasp_amd.h.  The variant of an explicit key (no device needed); key_bits, bit 0 upward:
+// nt, c16, windowed, win1, shared_ids, has_reg8, seven_waves, long16, row_tiles
+extern "C" const char *dasp_debug_spmv_variant(int precision, unsigned key_bits)
+{
+    const auto bit = [&](int i) { return (key_bits >> i & 1u) != 0; };
+    return dasp::select_spmv_variant({precision, bit(0), bit(1), bit(2), bit(3), bit(4), bit(5), bit(6), bit(7), bit(8)}).name;
+}
+// what launch_spmv would launch for this plan now: a variant's name, "two_phase", "panels" (a column-panel parent), "none" (an empty grid); null + the error text if it is not uploaded
+extern "C" const char *dasp_debug_plan_kernel(const dasp_plan_t *plan)
+{
+    if (!plan || !plan->impl.dev || !plan->impl.dev->arena) { dasp::set_error("plan not uploaded"); return nullptr; }
+    const dasp::Plan &p = plan->impl;
+    const dasp::DevArgs &a = p.dev->args;
+    return p.two_phase ? "two_phase" : !p.panels.empty() ? "panels" : a.wg_long + a.wg_med + a.wg_short + a.wg_rt > 0 ? dasp::select_spmv_variant(dasp::variant_key(p, *p.dev)).name : "none";
+}
+namespace dasp {
 
 namespace {
 // event pair / capture objects released on every return path

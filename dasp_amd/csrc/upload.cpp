@@ -120,8 +120,6 @@ long long shared_ids_net_saving(const Plan &p, const SharedIds &s, bool long16)
     (void)long16_rule(p, &narrow);
     return s.paired_id_bytes - s.shared_bytes - (long16 ? 2 * narrow : 0);
 }
-// is the shared kernel launched?  The plan streams from HBM (the line of the non-temporal policy) and the plane saves >= 3 % of its streamed bytes; DASP_SHARE_IDS=1 / 0
-// (read at upload) forces it on wherever a plane can be derived / off
 // DevicePlan::seven_waves (device.hpp): most of the regular chunks sit in one-shot blocks of a bandwidth-bound f64 plan
 static bool seven_waves_rule(const Plan &p)
 {
@@ -141,6 +139,8 @@ static bool seven_waves_rule(const Plan &p)
     }
     return on;
 }
+// is the shared kernel launched?  The plan streams from HBM (the line of the non-temporal policy) and the plane saves >= 3 % of its streamed bytes; DASP_SHARE_IDS=1 / 0
+// (read at upload) forces it on wherever a plane can be derived / off
 static int share_ids_env() { const char *e = std::getenv("DASP_SHARE_IDS"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }
 static bool shared_ids_rule(const Plan &p, const SharedIds &s)
 {

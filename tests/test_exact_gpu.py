@@ -6,7 +6,8 @@ any row length -- and one mis-gathered column, one dropped tail element or one v
 relative checks of tests/test_gpu_spmv.py cannot see such an error in an f16 row of more than about a hundred nonzeros; the last test here shows it.)
 
 run_form() runs one form: the plan is built with the form's options in both y orders, the plan's own counters must say that the form under test was
-taken (else the test FAILS: nothing here skips), y is prefilled with NaN, two seeds, then y += A x onto small multiples of 8, then the non-finite
+taken (else the test FAILS: nothing here skips), the uploaded plan must name the kernel the case is about (kernel=: Plan.kernel_variant(), the launch
+decision itself -- kernels.hip select_spmv_variant, whose rungs the comments below number as DESIGN.md section 4 does), y is prefilled with NaN, two seeds, then y += A x onto small multiples of 8, then the non-finite
 variants: x[j] = inf for one column, and a nan / inf / -inf value in one long, one medium and one short row -- the non-finite rows must be exactly
 the poisoned ones and every other row exactly equal (a pad that multiplies its 0 by x, or a sum that mixes rows, fails here).
 
@@ -66,9 +67,9 @@ def expect_nonfinite(got, mask, want, what):
     expect_equal(got[~mask], want[~mask], what)
 
 
-def run_form(dasp, torch, name, prec, kw, taken, layout=None, shift=0, env=None, taken_after_upload=None):
+def run_form(dasp, torch, name, prec, kw, taken, layout=None, shift=0, env=None, taken_after_upload=None, kernel=None):
     """one form on one pattern: see the module docstring.  taken(plan) asserts from the plan's own counters that the form was taken; layout(x) gives
-    the buffer the plan reads x from (partitioned x)."""
+    the buffer the plan reads x from (partitioned x); kernel: what the uploaded plan's kernel_variant() must say."""
     dt = np_dtype(prec)
     layout = layout or (lambda x: x)
     rp, ci, n = X.pattern(name)
@@ -81,6 +82,8 @@ def run_form(dasp, torch, name, prec, kw, taken, layout=None, shift=0, env=None,
             plan = dasp.Plan(rp, ci, a.astype(dt), n, precision=prec, y_order=y_order, **kw)
             taken(plan)
             upload(plan, env or {})
+            if kernel is not None:
+                assert plan.kernel_variant() == kernel, (what, plan.kernel_variant())
             if taken_after_upload:
                 taken_after_upload(plan)
             perm = plan.order_rid if y_order == dasp.Y_PERMUTED else np.arange(m)
@@ -93,6 +96,7 @@ def run_form(dasp, torch, name, prec, kw, taken, layout=None, shift=0, env=None,
                     p2 = dasp.Plan(rp, ci, a2.astype(dt), n, precision=prec, y_order=y_order, **kw)
                     taken(p2)
                     upload(p2, env or {})
+                    assert kernel is None or p2.kernel_variant() == kernel, (what, tag, p2.kernel_variant())
                 expect_nonfinite(product(torch, p2, layout(x2), m, prec, shift=shift), mask[perm], want[perm], what + (tag,))
                 if p2 is not plan:
                     p2.close()
@@ -101,6 +105,10 @@ def run_form(dasp, torch, name, prec, kw, taken, layout=None, shift=0, env=None,
 
 def lens_of(name):
     return np.diff(X.pattern(name)[0])
+
+
+def tname(prec):
+    return "double" if prec == 64 else "half"
 
 
 # ---------------------------------------------------------------------------------------------------------------- plain DASP blocks
@@ -128,7 +136,14 @@ def test_plain_blocks(dasp, torch_cuda, name, cid16, pairs, prec):
     def taken(plan):
         taken_plain(name, cid16, pairs)(plan)
         assert plan.stats["n_med_blocks"] > 0 and plan.host_array("irr_ptr")[-1] > 0         # MFMA blocks, and tail entries behind them
-    run_form(dasp, torch_cuda, name, prec, dict(PLAIN, cid16=cid16, chunk_pairs=pairs), taken)
+    c16 = int(cid16 == 1)
+    if name != "HV15R":                              # mixed, ljournal-2008: narrow long pieces hold >= 5 % of the nonzeros -- the builds that read their 16-bit ids (rung 4)
+        kernel = "dasp_spmv_kernel<%s,0,%d,0,0,0,1>" % (tname(prec), c16)
+    elif prec == 64 and c16 and pairs != -1:         # HV15R, f64, 16-bit ids, paired chunks: its pipelined blocks carry one-byte ids (rung 3)
+        kernel = "dasp_spmv_kernel<double,0,1,0,1,0,0>"
+    else:                                            # the plain build (rung 6)
+        kernel = "dasp_spmv_kernel<%s,0,%d,0,0,0,0>" % (tname(prec), c16)
+    run_form(dasp, torch_cuda, name, prec, dict(PLAIN, cid16=cid16, chunk_pairs=pairs), taken, kernel=kernel)
 
 
 @pytest.mark.parametrize("prec", [64, 16])
@@ -173,7 +188,20 @@ def test_one_byte_ids_f64(dasp, torch_cuda, name, kw, where):
         else:
             assert 0 < st["cid8_chunks"] < plan.host_array("med_ptr")[-1]                        # narrow AND wide chunks
             assert (piped if where == "pipelined" else shot) > 0
-    run_form(dasp, torch_cuda, name, 64, dict(PLAIN, **kw), taken)
+    run_form(dasp, torch_cuda, name, 64, dict(PLAIN, **kw), taken, kernel="dasp_spmv_kernel<double,0,1,0,%d,0,0>" % (where != "off"))      # rung 3 / rung 6
+
+
+@pytest.mark.parametrize("name,kw,kernel", [("HV15R", dict(cid8=1), "dasp_spmv_kernel<double,0,1,0,1,7,0>"), ("banded4", dict(cid8=1, chunk_pairs=2, slab_max_len=4), "dasp_spmv_kernel<double,0,1,0,1,7,0>"),
+                                             ("mixed", dict(cid8=1), "dasp_spmv_kernel<double,0,1,0,0,7,0>"), ("mixed", dict(cid8=-1), "dasp_spmv_kernel<double,0,1,0,0,7,0>")])
+def test_seven_wave_builds_f64(dasp, torch_cuda, name, kw, kernel):
+    """DASP_SEVEN_WAVES=1 (read at upload): the f64 builds held to 7 waves per SIMD.  With one-byte ids in the plan the one-byte-id build of them (rung 3 with
+    MW = 7: HV15R in pipelined blocks, banded4 in one-shot blocks), without them the build with 16-bit ids (rung 5) -- although `mixed` has the narrow long
+    pieces of rung 4.  No chunk of `mixed` spans fewer than 255 columns, so that pattern carries no one-byte ids whatever cid8 asks for: both of its plans are rung 5."""
+    def taken(plan):
+        st = plan.stats
+        assert st["cid16_on"] == 1 and st["x_window_on"] == 0 and plan.n_panels == 0 and st["n_med_blocks"] > 0
+        assert (st["cid8_chunks"] > 0) == (name != "mixed")
+    run_form(dasp, torch_cuda, name, 64, dict(PLAIN, cid16=1, **kw), taken, env={"DASP_SEVEN_WAVES": "1"}, kernel=kernel)
 
 
 # ---------------------------------------------------------------------------------------------------------------- long rows
@@ -191,7 +219,20 @@ def test_long_rows(dasp, torch_cuda, long_piece, prec):
             assert np.diff(pp).max() <= 256 and st["n_long_multi"] == 9
         else:
             assert c16[:, 1].any() and not c16[:, 1].all()                                        # 16-bit AND 32-bit pieces
-    run_form(dasp, torch_cuda, "long", prec, dict(long_piece=long_piece, col_panels=-1, two_phase=-1), taken)
+    # narrow pieces (16-bit ids) hold nearly all nonzeros: rung 4 -- but for f16 pieces of 256, which are too short for 16-bit ids (fewer than four chunks): rung 6
+    l16 = int(prec == 64 or long_piece == 0)
+    run_form(dasp, torch_cuda, "long", prec, dict(long_piece=long_piece, col_panels=-1, two_phase=-1), taken, kernel="dasp_spmv_kernel<%s,0,0,0,0,0,%d>" % (tname(prec), l16))
+
+
+@pytest.mark.parametrize("prec", [64, 16])
+def test_long_rows_16_bit_ids_forced(dasp, torch_cuda, prec):
+    """DASP_LONG16=1 (read at upload): the builds that read the 16-bit ids of narrow long pieces, whatever share of the nonzeros those pieces hold (rung 4)"""
+    def taken(plan):
+        st = plan.stats
+        c16 = plan.host_array("piece_c16").reshape(-1, 2)
+        assert st["row_long"] == 10 and st["n_long_multi"] > 0 and plan.n_panels == 0 and st["two_phase"] == 0 and st["x_window_on"] == 0
+        assert c16[:, 1].any() and not c16[:, 1].all()                                        # 16-bit AND 32-bit pieces
+    run_form(dasp, torch_cuda, "long", prec, dict(col_panels=-1, two_phase=-1), taken, env={"DASP_LONG16": "1"}, kernel="dasp_spmv_kernel<%s,0,0,0,0,0,1>" % tname(prec))
 
 
 @pytest.mark.parametrize("prec", [64, 16])
@@ -249,7 +290,8 @@ def test_lds_x_windows(dasp, torch_cuda, row_window, prec):
     def taken(plan):
         st = plan.stats
         assert st["x_window_on"] == 1 and st["row_window"] == row_window and st["n_windows_lds"] == st["n_windows"] > 0 and st["x_window_hybrid"] == 0
-    run_form(dasp, torch_cuda, "banded", prec, dict(x_window=81920, row_window=row_window, col_panels=-1, two_phase=-1), taken)
+    # 63 or 4 windows: fewer than the device has CUs, so the one-window-per-CU build (rung 1)
+    run_form(dasp, torch_cuda, "banded", prec, dict(x_window=81920, row_window=row_window, col_panels=-1, two_phase=-1), taken, kernel="dasp_spmv_win1_kernel<%s,1>" % tname(prec))
 
 
 @pytest.mark.parametrize("prec", [64, 16])
@@ -272,7 +314,14 @@ def test_column_panels(dasp, torch_cuda, kw, prec):
         assert plan.n_panels == kw["col_panels"] == st["n_col_panels"] and st["two_phase"] == 0 and st["lcb_rows"] == 0
         if "row_tile_max" in kw:
             assert st["row_tile_max"] == kw["row_tile_max"] and st["row_tile_nnz"] > 0 and st["n_row_tiles"] > 0
-    run_form(dasp, torch_cuda, "mixed", prec, dict(two_phase=-1, long_cb=-1, **kw), taken)
+
+    def children(plan):
+        for k in range(plan.n_panels):
+            sub = plan.panel(k)[0]
+            if sub.stats["n_row_tiles"] > 0:          # a panel with row tiles launched by itself runs the row-tile build (rung 0)
+                assert sub.kernel_variant() == "dasp_spmv_rt_kernel<%s,0,%d>" % (tname(prec), sub.stats["cid16_on"]), (k, sub.kernel_variant())
+        assert "row_tile_max" not in kw or all(plan.panel(k)[0].stats["n_row_tiles"] > 0 for k in range(plan.n_panels))
+    run_form(dasp, torch_cuda, "mixed", prec, dict(two_phase=-1, long_cb=-1, **kw), taken, kernel="panels", taken_after_upload=children)
 
 
 @pytest.mark.parametrize("prec", [64, 16])
@@ -295,7 +344,7 @@ def test_two_phase(dasp, torch_cuda, name, kw):
         assert st["two_phase"] == 1 and st["tp_segments"] > 0 and plan.n_panels == 0 and st["lcb_rows"] == 0
         if kw:
             assert st["tp_col_block"] == kw["tp_col_block"] and 0 < np.diff(plan.host_array("tp_rb_row0")).max() <= kw["tp_row_block"]
-    run_form(dasp, torch_cuda, name, 16, dict(two_phase=1, long_cb=-1, **kw), taken)
+    run_form(dasp, torch_cuda, name, 16, dict(two_phase=1, long_cb=-1, **kw), taken, kernel="two_phase")
 
 
 def test_two_phase_with_hub_rows(dasp, torch_cuda):
@@ -357,7 +406,7 @@ def test_shared_column_ids_of_twin_rows_f64(dasp, torch_cuda):
 
     def in_use(plan):
         assert plan.shared_ids()["in_use"]
-    run_form(dasp, torch_cuda, "twins", 64, dict(cid16=1, cid8=1, x_window=-1), taken, env={"DASP_SHARE_IDS": "1"}, taken_after_upload=in_use)
+    run_form(dasp, torch_cuda, "twins", 64, dict(cid16=1, cid8=1, x_window=-1), taken, env={"DASP_SHARE_IDS": "1"}, taken_after_upload=in_use, kernel="dasp_spmv_shared_kernel<0>")      # rung 2
 
 
 # ---------------------------------------------------------------------------------------------------------------- forms that meet
