@@ -315,6 +315,16 @@ class Plan:
         """1 for a two-phase plan in exact mode, else 0."""
         return int(_lib.lib().dasp_plan_tp_exact(self._h))
 
+    def set_hub_exact(self, on):
+        """Exact, bit-reproducible sums for the hub rows of a hybrid plan (f16, two-phase, column-blocked long rows) on (1) / off (0)
+        (dasp_plan_set_hub_exact): needs no GPU, takes effect with the next launch, independent of set_tp_exact; no effect on any other plan."""
+        _lib.check(_lib.lib().dasp_plan_set_hub_exact(self._h, int(on)))
+
+    @property
+    def hub_exact(self):
+        """1 for a two-phase plan with hub rows whose hub kernels are the exact ones, else 0."""
+        return int(_lib.lib().dasp_plan_hub_exact(self._h))
+
     def spmv(self, dX, dY, stream=0, accumulate=False):
         """dX, dY: integer device addresses (e.g. torch_tensor.data_ptr()); stream: hipStream_t as int.
         accumulate: y += A x instead of y = A x (dasp_plan_spmv_acc)."""

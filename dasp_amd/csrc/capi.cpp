@@ -398,6 +398,14 @@ int dasp_plan_set_tp_exact(dasp_plan_t *plan, int on)
 
 int dasp_plan_tp_exact(const dasp_plan_t *plan) { return plan && plan->impl.two_phase && plan->impl.tp_exact ? 1 : 0; }
 
+int dasp_plan_set_hub_exact(dasp_plan_t *plan, int on)
+{
+    if (!plan) return DASP_ERR_ARG;
+    return guarded("dasp_plan_set_hub_exact", [&] { return set_hub_exact(plan->impl, on); });
+}
+
+int dasp_plan_hub_exact(const dasp_plan_t *plan) { return plan && has_exact_hub_kernels(plan->impl) && plan->impl.hub_exact ? 1 : 0; }
+
 // the host mirror of dasp_tp_reduce_exact_kernel's arithmetic, from the same header: what exact mode stores for a row of these products
 int dasp_tp_exact_dot_f16(const uint16_t *a, const uint16_t *x, long long n, int accumulate, uint16_t y_in, uint16_t *y_out)
 {

@@ -82,6 +82,10 @@ struct TpDev {
 struct LcbDev {
     const void *val; const unsigned short *lcol; const int *ptr; const int *unit; const int *row_dst; void *partial;
     int n_units, n_rows, n_cb, cb, xlen;
+    // the exact partial planes of an f16 two-phase hybrid (DevicePlan::lcb_xpart; null otherwise): per (block, row) piece, CB-major like `partial`, the piece's sum as the two
+    // 64-bit integers of tp_exact.hpp and its flags -- H[n_cb * n_rows] (8 bytes each), then L (8), then the flags (4)
+    void *xpart;
+    int xsteps;      // steps of the plan's longest unit: what the exact kernel's three LDS planes of step sums are sized by (<= kLcbUnitElems / kLcbStep + kLcbUnitPieces)
 };
 
 // byte offsets of the nnz-sized arrays inside the arena (devpack.hip writes them, tests download them)
@@ -103,6 +107,9 @@ struct DevicePlan {
     DevArgs args{};
     TpDev tp{};             // Plan::two_phase: the arena holds the tile streams, `args` is unused
     LcbDev lcb{};           // a column-panel parent with column-blocked long rows: its arrays follow the partial-result buffers in the arena
+    // an f16 two-phase plan with hub rows: what the exact hub kernels write and read (LcbDev::xpart), n_cb x n_rows x 20 bytes in an allocation of its own (the arena is
+    // byte for byte the same with or without it), zero-filled at upload: empty (row, block) pieces are never written
+    void *lcb_xpart = nullptr;
     bool nt = false;
     bool win1 = false;      // windowed plan with at most one window workgroup per CU: launch dasp_spmv_win1_kernel
     // f64, no windows: most of the regular chunks sit in ONE-SHOT blocks (rows of <= 32: all of a block's loads in flight at once, a wave's life is two memory round

@@ -500,6 +500,132 @@ __global__ __launch_bounds__(256) void dasp_lcb_reduce_kernel(LcbDev a, T *__res
     if (lane == 0) { const int d = a.row_dst[i]; part0[d] = acc ? (T)((part_t)part0[d] + s) : (T)s; }
 }
 
+// ---- the hub rows of a two-phase hybrid, exact (Plan::hub_exact, dasp_plan_set_hub_exact; the arithmetic and its bounds: tp_exact.hpp).  The same grid, units, x staging,
+// 16-byte loads and U = 4 steps in flight as dasp_lcb_kernel<_Float16>, over the same four lcb arrays.  A lane's 8 products (pads skipped: they reach neither x nor the
+// flags) are split and added as a Pair; the 16 lanes of a step combine their Pairs with the same DPP moves (128 products: still exact in f64, tpx::kMaxPairTerms) and OR
+// their flags; lane 0 parks the step's (H, L, flags) in LDS -- 20 bytes per step in three planes instead of 8.  After the barrier one thread per piece adds the piece's
+// step sums as integers and STORES (H, L, flags) into the exact partial planes (LcbDev::xpart): no atomics anywhere, and flags that are rewritten by every launch.
+// The three LDS planes hold LcbDev::xsteps entries each, the steps of the plan's longest unit (at most kLcbUnitElems / kLcbStep + kLcbUnitPieces = 1280: 89 KiB with
+// the default slice of x); a plan whose units stay near 256 steps keeps two workgroups per CU, as the f32 kernel does.
+template <int CTRL>
+__device__ __forceinline__ long long dpp_mov_i64(long long v)
+{
+    int lo = (int)(unsigned long long)v, hi = (int)((unsigned long long)v >> 32);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+__global__ __launch_bounds__(1024) void dasp_lcb_exact_kernel(LcbDev a, const _Float16 *__restrict__ x)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    constexpr int A = 8;
+    typedef _Float16 vecA __attribute__((ext_vector_type(A)));
+    typedef unsigned short colA __attribute__((ext_vector_type(A)));
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    _Float16 *xl = reinterpret_cast<_Float16 *>(lds_raw);
+    const int u = blockIdx.x;
+    const int c = a.unit[3 * u], q0 = a.unit[3 * u + 1], q1 = a.unit[3 * u + 2];
+    const int c0 = c * a.cb, len = min(a.cb, a.xlen - c0);
+    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+        for (int i = threadIdx.x * A; i < len; i += 1024 * A) {
+            if (i + A <= len) *reinterpret_cast<vecA *>(xl + i) = *reinterpret_cast<const vecA *>(x + c0 + i);
+            else for (int j = i; j < len; ++j) xl[j] = x[c0 + j];
+        }
+    } else for (int i = threadIdx.x; i < len; i += 1024) xl[i] = x[c0 + i];
+    __syncthreads();
+    constexpr int G = kLcbStep / A, SPW = 64 / G;         // 16 lanes per step, four steps per wave instruction
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane / G, l = lane % G;
+    long long *stH = reinterpret_cast<long long *>(lds_raw + (((size_t)a.cb * 2 + 15) & ~size_t(15))), *stL = stH + a.xsteps;
+    unsigned *stF = reinterpret_cast<unsigned *>(stL + a.xsteps);
+    const int np = q1 - q0;
+    const _Float16 *val = static_cast<const _Float16 *>(a.val);
+    const int S0 = a.ptr[q0] / kLcbStep, S1 = a.ptr[q1] / kLcbStep;
+    constexpr int U = 4;
+    for (int sb = S0 + wave * SPW * U; sb < S1; sb += 16 * SPW * U) {
+        vecA v[U]; colA lc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int st = min(sb + u * SPW + g, S1 - 1);          // (a step past the end re-reads the last one; its sum is dropped below)
+            const size_t e = (size_t)st * kLcbStep + (size_t)l * A;
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const vecA *>(val + e));
+            lc[u] = __builtin_nontemporal_load(reinterpret_cast<const colA *>(a.lcol + e));
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            vecA xv;
+            float p[A];
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                const bool pad = lc[u][j] == kLcbPadCol;
+                const _Float16 xj = xl[pad ? 0 : lc[u][j]];
+                xv[j] = pad ? (_Float16)0 : xj;
+                p[j] = pad ? 0.0f : (float)v[u][j] * (float)xj;
+            }
+            // non-finite products: where an operand is (tested on the packed bit patterns, as the exact phase 2 does); they set their flag and leave the sums
+            unsigned fl = 0u;
+            const u32x4 vb = __builtin_bit_cast(u32x4, v[u]), xb = __builtin_bit_cast(u32x4, xv);
+            if ((tpx::nonfinite_f16x2(vb[0]) | tpx::nonfinite_f16x2(vb[1]) | tpx::nonfinite_f16x2(vb[2]) | tpx::nonfinite_f16x2(vb[3]) |
+                 tpx::nonfinite_f16x2(xb[0]) | tpx::nonfinite_f16x2(xb[1]) | tpx::nonfinite_f16x2(xb[2]) | tpx::nonfinite_f16x2(xb[3])) != 0u) {
+#pragma unroll
+                for (int j = 0; j < A; ++j) {
+                    const unsigned f = tpx::flag_of(p[j]);
+                    fl |= f;
+                    if (f) p[j] = 0.0f;
+                }
+            }
+            tpx::Pair run = tpx::split(p[0]);
+#pragma unroll
+            for (int j = 1; j < A; ++j) run = tpx::add(run, tpx::split(p[j]));
+#define DASP_LCB_XSUM(CTRL) { run = tpx::add(run, tpx::Pair{dpp_mov_f64<CTRL>(run.hi), dpp_mov_f64<CTRL>(run.lo)}); fl |= (unsigned)__builtin_amdgcn_update_dpp((int)fl, (int)fl, CTRL, 0xf, 0xf, false); }
+            DASP_LCB_XSUM(0x128) DASP_LCB_XSUM(0x124) DASP_LCB_XSUM(0x122) DASP_LCB_XSUM(0x121)      // row_ror 8, 4, 2, 1: every lane of the step holds its sum
+#undef DASP_LCB_XSUM
+            const int st = sb + u * SPW + g;
+            if (l == 0 && st < S1) { const tpx::Fixed f = tpx::to_fixed(run); stH[st - S0] = f.H; stL[st - S0] = f.L; stF[st - S0] = fl; }
+        }
+    }
+    __syncthreads();
+    const size_t planes = (size_t)a.n_cb * (size_t)a.n_rows;
+    long long *pH = static_cast<long long *>(a.xpart), *pL = pH + planes;
+    unsigned *pF = reinterpret_cast<unsigned *>(pL + planes);
+    for (int i = threadIdx.x; i < np; i += 1024) {
+        tpx::Fixed s{0, 0};
+        unsigned fl = 0u;
+        for (int st = a.ptr[q0 + i] / kLcbStep - S0, se = a.ptr[q0 + i + 1] / kLcbStep - S0; st < se; ++st) { s = tpx::add(s, tpx::Fixed{stH[st], stL[st]}); fl |= stF[st]; }
+        pH[q0 + i] = s.H; pL[q0 + i] = s.L; pF[q0 + i] = fl;
+    }
+}
+// one wave per hub row: its n_cb exact partials added as integers (lanes stride over the blocks, then 64-bit adds across the lanes), the flags ORed; lane 0 rounds once
+// (tpx::finish) and adds into y BEHIND phase 2, like dasp_lcb_reduce_kernel(..., 1): y[dst] = (f16)((f32)y[dst] + (f32)d)
+__global__ __launch_bounds__(256) void dasp_lcb_reduce_exact_kernel(LcbDev a, _Float16 *__restrict__ y)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
+    if (i >= a.n_rows) return;
+    const size_t planes = (size_t)a.n_cb * (size_t)a.n_rows;
+    const long long *pH = static_cast<const long long *>(a.xpart), *pL = pH + planes;
+    const unsigned *pF = reinterpret_cast<const unsigned *>(pL + planes);
+    tpx::Fixed s{0, 0};
+    unsigned fl = 0u;
+    for (int c = lane; c < a.n_cb; c += kWave) {
+        const size_t q = (size_t)c * (size_t)a.n_rows + (size_t)i;
+        s = tpx::add(s, tpx::Fixed{pH[q], pL[q]}); fl |= pF[q];
+    }
+#define DASP_LCB_XSUM(CTRL) { s = tpx::add(s, tpx::Fixed{dpp_mov_i64<CTRL>(s.H), dpp_mov_i64<CTRL>(s.L)}); fl |= (unsigned)__builtin_amdgcn_update_dpp((int)fl, (int)fl, CTRL, 0xf, 0xf, false); }
+    DASP_LCB_XSUM(0x128) DASP_LCB_XSUM(0x124) DASP_LCB_XSUM(0x122) DASP_LCB_XSUM(0x121)
+#undef DASP_LCB_XSUM
+    auto row_of = [&](long long v, int r) { return (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)v >> 32), r) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(unsigned long long)v, r)); };
+    tpx::Fixed t{row_of(s.H, 0), row_of(s.L, 0)};
+    unsigned ft = (unsigned)__builtin_amdgcn_readlane((int)fl, 0);
+#pragma unroll
+    for (int r = 16; r < 64; r += 16) { t = tpx::add(t, tpx::Fixed{row_of(s.H, r), row_of(s.L, r)}); ft |= (unsigned)__builtin_amdgcn_readlane((int)fl, r); }
+    if (lane == 0) {
+        const double d = tpx::finish(t, ft & 7u);
+        const int dst = a.row_dst[i];
+        y[dst] = (_Float16)((float)y[dst] + (float)d);
+    }
+}
+
 #ifdef DASP_STAMPS
 int g_stamp_launch = -1;          // host: the number the next stamped launch carries (-1: stamps off)
 }  // namespace dasp
@@ -652,7 +778,7 @@ int set_stream_policy(Plan &p, int policy)
 int tp_kernels_allow_lds()
 {
     for (const void *fn : {reinterpret_cast<const void *>(&dasp_tp_expand_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_tp_reduce_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_tp_reduce_exact_kernel),
-                           reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_lcb_kernel<double>)})
+                           reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_lcb_kernel<double>), reinterpret_cast<const void *>(&dasp_lcb_exact_kernel)})
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return DASP_OK;
 }
@@ -692,6 +818,9 @@ static int launch_panels_merged(Plan &p, const void *dX, char *part, size_t stri
 // the column-blocked long rows (Plan::lcb): the streaming kernel's dynamic LDS = the block's slice of x + 16 + one sum per step and piece of a unit
 template <class T>
 static size_t lcb_lds_bytes(const LcbDev &q) { return (size_t)q.cb * sizeof(T) + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8; }
+// the exact hub kernel: 20 bytes per step of the plan's longest unit (two 64-bit planes and a word of flags) behind the f16 slice of x -- up to 89 KiB at the default
+// column block, above the 64 KiB default
+static size_t lcb_exact_lds_bytes(const LcbDev &q) { return (size_t)q.cb * 2 + 16 + (size_t)q.xsteps * 20; }
 // a column-panel parent: the panels' products into their partial results, the hub rows, then y = (y +) the sum of the partial results
 template <class T>
 static int launch_panels(Plan &p, const void *dX, void *dY, void *stream, bool accumulate)
@@ -730,16 +859,19 @@ int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate
         hipStream_t s = static_cast<hipStream_t>(stream);
         // the hybrid's hub rows (Plan::lcb): their streaming kernel, then -- BEHIND phase 2, which stores 0 at their positions or leaves y alone in accumulate mode -- their
         // per-row sums added into y
-        const bool hub = p.lcb.n_rows() > 0;
+        const bool hub = p.lcb.n_rows() > 0, hub_exact = hub && p.hub_exact;      // exact hub rows (dasp_plan_set_hub_exact): the other pair of hub kernels, in the same places
         const LcbDev &q = p.dev->lcb;
-        if (hub) hipLaunchKernelGGL((dasp_lcb_kernel<_Float16>), dim3(q.n_units), dim3(1024), lcb_lds_bytes<_Float16>(q), s, q, static_cast<const _Float16 *>(dX));
+        if (hub_exact && !q.xpart) { set_error("hub_exact: the plan has no exact partial planes"); return DASP_ERR_STATE; }
+        if (hub_exact) hipLaunchKernelGGL(dasp_lcb_exact_kernel, dim3(q.n_units), dim3(1024), lcb_exact_lds_bytes(q), s, q, static_cast<const _Float16 *>(dX));
+        else if (hub) hipLaunchKernelGGL((dasp_lcb_kernel<_Float16>), dim3(q.n_units), dim3(1024), lcb_lds_bytes<_Float16>(q), s, q, static_cast<const _Float16 *>(dX));
         if (a.n_units > 0)
             hipLaunchKernelGGL((dasp_tp_expand_kernel<_Float16>), dim3(a.n_units), dim3(512), (size_t)a.cb * 2, s, a, static_cast<const _Float16 *>(dX));
         if (a.n_rb > 0 && p.tp_exact)      // exact sums (dasp_plan_set_tp_exact): two 64-bit integers and 4 flag bits per output position
             hipLaunchKernelGGL(dasp_tp_reduce_exact_kernel, dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 16 + (size_t)((a.rb_max + 7) / 8) * 4, s, a, static_cast<_Float16 *>(dY), accumulate ? 1 : 0);
         else if (a.n_rb > 0)
             hipLaunchKernelGGL((dasp_tp_reduce_kernel<_Float16>), dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 8, s, a, static_cast<_Float16 *>(dY), accumulate ? 1 : 0);
-        if (hub) hipLaunchKernelGGL((dasp_lcb_reduce_kernel<_Float16>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, static_cast<_Float16 *>(dY), 1);
+        if (hub_exact) hipLaunchKernelGGL(dasp_lcb_reduce_exact_kernel, dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, static_cast<_Float16 *>(dY));
+        else if (hub) hipLaunchKernelGGL((dasp_lcb_reduce_kernel<_Float16>), dim3((q.n_rows + kWavesPerWG - 1) / kWavesPerWG), dim3(256), 0, s, q, static_cast<_Float16 *>(dY), 1);
         HIP_TRY(hipGetLastError());
         return DASP_OK;
     }

@@ -47,7 +47,7 @@ void lcb_rows(Plan &p, const int *rp, const std::vector<unsigned char> &in_lcb, 
     L = LongCB{};
     L.cb = lcb_col_block(p); L.n_cb = std::max(1, (p.n + L.cb - 1) / L.cb);
     L.h = 1 << 30;
-    for (int i = 0; i < p.m; ++i) if (in_lcb[(size_t)i]) { L.row_id.push_back(i); L.row_dst.push_back(slot_of_row ? slot_of_row[i] : i); L.h = std::min(L.h, rp[i + 1] - rp[i]); }
+    for (int i = 0; i < p.m; ++i) if (in_lcb[(size_t)i]) { L.row_id.push_back(i); L.row_dst.push_back(slot_of_row ? slot_of_row[i] : i); L.h = std::min(L.h, rp[i + 1] - rp[i]); L.max_row = std::max<long long>(L.max_row, rp[i + 1] - rp[i]); }
 }
 // element offsets of the pieces (cnt: elements of every piece, CB-major), each padded to whole steps
 int lcb_offsets(LongCB &L, const std::vector<int> &cnt)
@@ -132,6 +132,29 @@ int build_long_cb_device(Plan &p, const int *rp, const DevCsr &d, const std::vec
     if (rc == DASP_OK) rc = lcb_units(L);
     if (rc != DASP_OK) pieces = DevTiles{};
     return rc;
+}
+
+long long lcb_longest_row(const LongCB &L)
+{
+    const size_t nL = (size_t)L.n_rows();
+    if (nL == 0 || L.ptr.size() != (size_t)L.n_cb * nL + 1 || L.lcol.size() != L.elems) return 0;
+    std::vector<long long> cnt(nL, 0);
+    for (size_t q = 0; q + 1 < L.ptr.size(); ++q)
+        for (int e = L.ptr[q]; e < L.ptr[q + 1]; ++e) cnt[q % nL] += L.lcol[(size_t)e] != kLcbPadCol;
+    return *std::max_element(cnt.begin(), cnt.end());
+}
+
+// The hub rows' exact sums are the two 64-bit integers of tp_exact.hpp: the same bound on the products of one row as the streams' (set_tp_exact, twophase.cpp).
+int set_hub_exact(Plan &p, int on)
+{
+    if (on != 0 && on != 1) { set_error("hub_exact must be 0 or 1"); return DASP_ERR_ARG; }
+    if (!has_exact_hub_kernels(p)) return DASP_OK;          // no hub rows, or a form whose other rows are not exact either
+    if (on && p.lcb.max_row >= (1ll << 22)) {
+        set_error("hub_exact: a hub row has " + std::to_string(p.lcb.max_row) + " nonzeros; the exact 64-bit sums hold fewer than 4194304 per row");
+        return DASP_ERR_ARG;
+    }
+    p.hub_exact = on == 1;
+    return DASP_OK;
 }
 
 bool validate_long_cb(const Plan &p, int n_panels, std::string &why)

@@ -230,6 +230,7 @@ struct LongCB {
     raw_vector<char> val;             // [elems * vbytes]
     std::vector<uint32_t> map;        // [elems] value map of val (opt.value_map); empty without one
     size_t elems = 0;
+    long long max_row = 0;            // nonzeros (pads not counted) of the longest hub row (not in a plan file: re-counted from lcol at load); what dasp_plan_set_hub_exact checks
     int n_rows() const { return (int)row_dst.size(); }
     int n_units() const { return (int)(unit.size() / 3); }
 };
@@ -338,6 +339,9 @@ struct Plan {
     // phase 2 sums exactly, in 64-bit integers (dasp_tp_reduce_exact_kernel, tp_exact.hpp): a launch-time switch over the same streams (opt.tp_exact,
     // dasp_plan_set_tp_exact); never set on a plan that is not two-phase, never stored in a plan file
     bool tp_exact = false;
+    // the hub rows of an f16 two-phase hybrid (lcb above) sum exactly too (dasp_lcb_exact_kernel / dasp_lcb_reduce_exact_kernel, tp_exact.hpp): a launch-time switch over the
+    // same lcb arrays (dasp_plan_set_hub_exact), independent of tp_exact; never set on any other plan, never stored in a plan file
+    bool hub_exact = false;
 
     // value map (opt.value_map = 1): for every stored slot of a value array, 1 + the index of the nonzero of the CALLER's CSR it holds (through
     // the column sort and the panel split), 0 for a pad.  Same element counts as the value arrays; every nonzero appears exactly once over all
@@ -474,6 +478,11 @@ bool validate_two_phase(const Plan &p, std::string &why);
 long long tp_longest_row(const TwoPhase &t);      // nonzeros of the longest row of the streams, counted from the host copy of lrow (a loaded plan's TwoPhase::max_row)
 // exact phase 2 on / off (dasp_plan_set_tp_exact): no effect on a plan that is not two-phase; DASP_ERR_ARG for another value or a row of >= 2^22 nonzeros in the streams
 int set_tp_exact(Plan &p, int on);
+// does the plan have hub rows that dasp_plan_set_hub_exact can switch: an f16 two-phase plan with column-blocked long rows
+inline bool has_exact_hub_kernels(const Plan &p) { return p.two_phase && p.precision == 16 && p.lcb.n_rows() > 0; }
+// exact hub rows on / off (dasp_plan_set_hub_exact): no effect on a plan without such rows; DASP_ERR_ARG for another value or a hub row of >= 2^22 nonzeros
+int set_hub_exact(Plan &p, int on);
+long long lcb_longest_row(const LongCB &L);      // nonzeros of the longest hub row, counted from the host copy of lcol (a loaded plan's LongCB::max_row)
 
 // column-blocked long rows (longcb.cpp): which rows (in_lcb[row] = 1) a column-panel plan of P panels hands to them (0 rows: none), the packer, the checks
 int decide_long_cb(const Plan &p, const int *rp, int P, std::vector<unsigned char> &in_lcb, int share_den = 4, int per_block = 64);

@@ -348,6 +348,7 @@ static bool read_plan(Reader &r, Plan &p, int depth, std::string &r_why)
     p.panel = depth > 0;
     if (!validate_plan(p, np, depth > 0, r_why)) return false;
     if (p.two_phase) p.tp.max_row = tp_longest_row(p.tp);      // (the file does not carry it; lrow has just been validated)
+    p.lcb.max_row = lcb_longest_row(p.lcb);                    // (nor the hub rows': counted from lcol, pads left out)
     p.opt.col_panels = np > 0 ? np : 1;
     for (int k = 0; k < np; ++k) {
         std::unique_ptr<dasp_plan> h(new dasp_plan());

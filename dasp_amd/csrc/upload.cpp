@@ -32,6 +32,7 @@ Plan::~Plan()
     if (dev) {
         value_map_free(dev);
         if (dev->arena) (void)hipFree(dev->arena);
+        if (dev->lcb_xpart) (void)hipFree(dev->lcb_xpart);
         if (dev->dargs) (void)hipFree(dev->dargs);
         std::free(dev->args_sent);
         delete dev;
@@ -88,6 +89,14 @@ static int upload_long_cb(Plan &p, DevicePlan *d, const LcbOffsets &o)
     q.val = base + o.v; q.lcol = (const unsigned short *)(base + o.c); q.ptr = (const int *)(base + o.p); q.unit = (const int *)(base + o.u);
     q.row_dst = (const int *)(base + o.d); q.partial = base + o.s;
     q.n_units = L.n_units(); q.n_rows = L.n_rows(); q.n_cb = L.n_cb; q.cb = L.cb; q.xlen = p.n;
+    q.xpart = nullptr; q.xsteps = 1;
+    for (int u = 0; u < L.n_units(); ++u) q.xsteps = std::max(q.xsteps, (L.ptr[(size_t)L.unit[3 * (size_t)u + 2]] - L.ptr[(size_t)L.unit[3 * (size_t)u + 1]]) / kLcbStep);
+    if (has_exact_hub_kernels(p)) {      // the exact partial planes (dasp_plan_set_hub_exact), whether the mode is on or not: the setter makes no GPU call
+        const size_t bytes = std::max<size_t>((size_t)L.n_cb * (size_t)L.n_rows() * 20, 16);
+        HIP_TRY(hipMalloc(&d->lcb_xpart, bytes));
+        HIP_TRY(hipMemset(d->lcb_xpart, 0, bytes));
+        q.xpart = d->lcb_xpart;
+    }
     if (int rc = tp_kernels_allow_lds()) return rc;
     return DASP_OK;
 }
@@ -154,7 +163,7 @@ static bool shared_ids_rule(const Plan &p, const SharedIds &s)
 
 void release_device(Plan &p)
 {
-    if (p.dev) { value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
+    if (p.dev) { value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->lcb_xpart) (void)hipFree(p.dev->lcb_xpart); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
 }
 
 int upload_plan(Plan &p);
@@ -212,7 +221,7 @@ static int upload_plan_impl(Plan &p)
         q.rb_row0 = (const int *)(base + o_r0); q.rb_seg0 = (const int *)(base + o_s0);
         q.n_units = t.n_units(); q.n_rb = t.n_rb(); q.cb = t.cb; q.rb_max = t.rb_max; q.xlen = p.n; q.m = p.m;
         d->nt = true;
-        if (lcb) if (int rc = upload_long_cb(p, d, lo)) return rc;
+        if (lcb) if (int rc = upload_long_cb(p, d, lo)) { release_device(p); return rc; }      // (the exact partial planes did not fit: nothing is left half-made)
         return tp_kernels_allow_lds();
     }
 

@@ -200,8 +200,8 @@ typedef struct dasp_options {
      *   dasp_plan_set_tp_exact switches an existing plan) makes this form reproducible AND exact: same streams, another phase-2 kernel.
      *   A caller who needs reproducible results should use tp_exact = 1, not two_phase = -1: on all four f16 graph stand-ins the exact form costs 5-12 % over the
      *   default mode and runs 1.4-2.7 x faster than the two_phase = -1 plan (ljournal-2008 0.175 / 0.184 / 0.418 ms, rmat_2M 0.082 / 0.086 / 0.133, ljournal-2008-uniform
-     *   0.175 / 0.186 / 0.499, powerlaw_1M 0.127 / 0.142 / 0.200: default / exact / two_phase = -1, profiles/r09_tp_exact.md).  two_phase = -1 remains the choice
-     *   where the hub rows of a hybrid plan must be exact too, or a row holds >= 2^22 nonzeros.
+     *   0.175 / 0.186 / 0.499, powerlaw_1M 0.127 / 0.142 / 0.200: default / exact / two_phase = -1, profiles/r09_tp_exact.md).  Where the hub rows of a hybrid plan must be exact too, call
+     *   dasp_plan_set_hub_exact(plan, 1) as well (below; profiles/r10_hub_exact.md); two_phase = -1 remains the choice only where a row holds >= 2^22 nonzeros.
      *   tp_col_block: columns per column block (multiple of 8, <= 65536; 0 = 32768); tp_row_block: most output positions per row block (<= 8192; 0 = 4096). */
     int two_phase;
     int tp_col_block, tp_row_block;
@@ -224,8 +224,8 @@ typedef struct dasp_options {
      * y = (f16)(f32)d (an empty row: +0);  dasp_plan_spmv_acc stores y = (f16)((f32)y_old + (f32)d).  A row with a NaN product (inf x 0 included) or with products of
      * both infinities gives NaN, a row with infinities of one sign that infinity; the finite products of such a row are ignored.  The result does not depend on the
      * run, on tp_col_block / tp_row_block, or on whether the host or the device packer built the plan; dasp_tp_exact_dot_f16 computes it on the host.
-     * The hub rows of a hybrid plan (long_cb: the column-blocked long rows) keep their kernels: they add in a fixed order -- reproducible from run to run -- but
-     * are NOT covered by "exact".
+     * The hub rows of a hybrid plan (long_cb: the column-blocked long rows) keep their kernels under this switch: they add in a fixed order -- reproducible from run
+     * to run -- but are NOT covered by "exact"; dasp_plan_set_hub_exact (below) is the switch that makes them exact too.
      *   0 = off (default), 1 = a plan that comes out two-phase starts in exact mode; every other value is DASP_ERR_ARG.  Plans that are not two-phase ignore it
      *   (they are deterministic already).  Packed arrays, order_rid, the stats and every automatic choice are those of the same plan with 0; a plan file does not
      *   store the mode (a loaded plan starts at 0).  DASP_ERR_ARG when a row of the streams holds >= 2^22 nonzeros (the 64-bit sums could overflow). */
@@ -390,6 +390,20 @@ int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);
 int dasp_plan_set_tp_exact(dasp_plan_t *plan, int on);
 /* 1 for a two-phase plan in exact mode, else 0 */
 int dasp_plan_tp_exact(const dasp_plan_t *plan);
+/* exact, bit-reproducible sums for the HUB rows of a hybrid plan on (1) / off (0, the state every plan starts in).  A hybrid is an f16 two-phase plan whose longest rows
+ * are column-blocked (dasp_stats_t::two_phase == 1 and lcb_rows > 0); with 1 its two hub kernels are replaced by a pair that keeps every (row, column block) piece as the
+ * two 64-bit integers of tp_exact, over the same packed arrays.  A hub row's result is then the one tp_exact defines: d = the EXACT sum of the row's f16 x f16 products
+ * rounded once to f64; dasp_plan_spmv leaves y = (f16)(f32)d, dasp_plan_spmv_acc y = (f16)((f32)y_old + (f32)d); NaN and infinities as there; dasp_tp_exact_dot_f16 is its
+ * host definition.  It does not depend on the run, on y_order, on the unit size, or on whether the host or the device packer built the plan.
+ * Independent of dasp_plan_set_tp_exact, which covers every OTHER row of the plan: either switch works alone, and both on is what "the whole plan exact" means.
+ * Host-built, device-built and loaded plans alike, uploaded or not; needs no GPU; takes effect with the next launch (do not switch while a capture of this plan's launches
+ * is replayed: a captured graph keeps the kernel it captured).  A plan file does not store the mode (a loaded plan starts at 0).  Costs 20 bytes per (hub row, column
+ * block) in a device allocation of its own, made at upload whether the mode is on or not.
+ * DASP_OK without effect on every other plan -- f64 plans, plans that are not two-phase, two-phase plans without hub rows, and column-panel plans (their panels are not
+ * exact, so exact hub rows would promise nothing there); DASP_ERR_ARG for another value, or when a hub row holds >= 2^22 nonzeros (the 64-bit sums could overflow). */
+int dasp_plan_set_hub_exact(dasp_plan_t *plan, int on);
+/* 1 for a two-phase plan with hub rows whose hub kernels are the exact ones, else 0 */
+int dasp_plan_hub_exact(const dasp_plan_t *plan);
 /* the host mirror of the exact phase 2 (same arithmetic header as the kernel): *y_out = what exact mode stores for a row whose n products are a[j] x[j]
  * (binary16 bit patterns) -- with accumulate = 1, onto y_in.  n < 2^22.  The definition of the result that tests and callers compare against. */
 int dasp_tp_exact_dot_f16(const uint16_t *a, const uint16_t *x, long long n, int accumulate, uint16_t y_in, uint16_t *y_out);
