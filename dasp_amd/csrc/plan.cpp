@@ -1,6 +1,22 @@
 // plan.cpp -- row classifier and the long / medium / short packers (host, multi-threaded).
 // Mirrors the host half of the reference's spmv_all (src/dasp_f64.h:499-1157,
 // src/dasp_f16.h:1029-1443) in the gfx950 geometry described in plan.hpp / DESIGN.md.
+//
+// What is in here, in order (DESIGN.md "plan creation"):
+//   resolve_threads, ab_knobs, Pool / parallel_for          the host's worker threads
+//   Remap, CsrProbe                                         column remap of a partitioned x; the questions the rules ask about the column ids, host or device CSR
+//   reference_geometry                                      the CUDA reference's padded sizes of the same input
+//   LapTimer, Build<T>                                      the DASP_VERBOSE stage timer; the state the stages of one build hand on
+//   validate_csr, sort_columns                              entry work of a whole plan
+//   lcb_counters, hub_rows, hybrid_then_tp, hybrid_then_tp_device, hybrid_then_tp_fetched     the two-phase / hybrid form from a host, a device, a fetched device CSR
+//   the stages of the DASP form, in the order run_stages calls them:
+//     classify_rows, sort_medium_by_length, measure_reference, assign_slots (+ slabs_pay),
+//     decide_windows (+ default_row_window, order_in_windows, scan_window_spans, fit_windows, hybrid_windows, windows_pay),
+//     medium_rows_as_pieces, pack_long, split_medium_chunks, pack_medium, pack_short, fill_stats, finish
+//   build_dasp                                              the DASP form for a metadata-only plan or one column panel
+//   build_form                                              which form a whole plan takes: two-phase / hybrid, column panels, or the plain DASP form
+//   decide_panels, build_panels                             the column panels
+//   build_plan                                              the entry point (plan.hpp)
 #include "plan.hpp"
 
 #include <algorithm>
@@ -167,15 +183,121 @@ struct Remap {
         return g * stride + (c - b[g]);
     }
 };
+
+// ---- the questions the packing rules ask about a matrix's column ids, answered from a host CSR (ci) or from a device CSR (dev: the devpack_* kernels
+// of devpack.hip, which apply the same remap) -- the one place that knows which of the two a build has.  Every method returns DASP_OK or a HIP failure.
+struct CsrProbe {
+    const Plan &p;
+    const int *rp, *ci;
+    const DevCsr *dev;
+    Remap remap;
+    int threads;
+    // line scatter of a row sample: over the first `cap` nonzeros of every row, the entries and how many of them lie on another line of x
+    // (2^shift columns) than their predecessor in the row.  The rows are not empty
+    int line_scatter(const std::vector<int> &rows, int shift, int cap, long long *lines, long long *entries) const
+    {
+        if (dev) return devpack_line_scatter(p, *dev, rows, lines, entries);
+        long long l = 0, n = 0;
+        for (int r : rows) {
+            const int b = rp[r], e = b + std::min(rp[r + 1] - b, cap);
+            int prev = remap(ci[b]) >> shift; l += 1;
+            for (int j = b + 1; j < e; ++j) { const int c = remap(ci[j]) >> shift; l += c != prev; prev = c; }
+            n += e - b;
+        }
+        *lines = l; *entries = n;
+        return DASP_OK;
+    }
+    // row coherence of pairs of equally long rows (pairs[2i], pairs[2i + 1]): entries compared, and how many lie within `within` columns of the
+    // other row's entry at the same position
+    int row_coherence(const std::vector<int> &pairs, int within, long long *near, long long *entries) const
+    {
+        if (dev) return devpack_row_coherence(p, *dev, pairs, within, near, entries);
+        long long nr = 0, n = 0;
+        for (size_t q = 0; q + 1 < pairs.size(); q += 2) {
+            const int a = rp[pairs[q]], b = rp[pairs[q + 1]], len = rp[pairs[q] + 1] - a;
+            for (int k = 0; k < len; ++k) { const int d = remap(ci[a + k]) - remap(ci[b + k]); nr += d > -within && d < within; }
+            n += len;
+        }
+        *near = nr; *entries = n;
+        return DASP_OK;
+    }
+    // span [lo, hi] and nonzeros of the windows over rows list[0 .. n): one window per R rows
+    int window_spans(const raw_vector<int> &list, int n, int R, int *lo_out, int *hi_out, long long *nnz_out) const
+    {
+        if (dev) return devpack_window_spans(p, *dev, list, R, lo_out, hi_out, nnz_out);
+        const int *const rp = this->rp, *const ci = this->ci;
+        const Remap remap = this->remap;
+        parallel_for(ceil_div(n, R), threads, 8, [&](long long w0, long long w1) {
+            for (long long w = w0; w < w1; ++w) {
+                const int a0 = (int)w * R, a1 = std::min(n, a0 + R);
+                int lo = 2147483647, hi = -1; long long k = 0;
+                for (int i = a0; i < a1; ++i) {
+                    const int r = list[(size_t)i];
+                    for (int j = rp[r]; j < rp[r + 1]; ++j) { const int c = remap(ci[j]); lo = std::min(lo, c); hi = std::max(hi, c); }
+                    k += rp[r + 1] - rp[r];
+                }
+                lo_out[w] = lo; hi_out[w] = hi; nnz_out[w] = k;
+            }
+        });
+        return DASP_OK;
+    }
+    // chunk spans of the medium blocks (16 rows of ridM / lenM each, nchunks[b] regular chunks of K columns): k16[b] = the first chunk of block b whose
+    // columns span more than 65534 (else nchunks[b]); narrow_mask (nullptr or [blocks]): bit c = chunk c (< 64) spans <= 254 columns
+    int chunk_spans(const raw_vector<int> &ridM, const raw_vector<int> &lenM, const std::vector<int> &nchunks, int K, int *k16_out, unsigned long long *narrow_mask) const
+    {
+        if (dev) return devpack_chunk_spans(p, *dev, ridM, lenM, nchunks, k16_out, narrow_mask);
+        const int *const rp = this->rp, *const ci = this->ci;
+        const Remap remap = this->remap;
+        const int nmed = (int)ridM.size();
+        parallel_for(ceil_div(nmed, kMedRows), threads, 256, [&](long long b0, long long b1) {
+            for (long long b = b0; b < b1; ++b) {
+                const int r0 = (int)b * kMedRows, r1 = std::min(nmed, r0 + kMedRows), k = nchunks[(size_t)b];
+                int k16 = k;
+                unsigned long long mask = 0;
+                for (int c = 0; c < k; ++c) {
+                    int lo = 2147483647, hi = -1;
+                    for (int r = r0; r < r1; ++r) {
+                        const int a0 = rp[ridM[r]], i0 = c * K, i1 = std::min(lenM[r], i0 + K);
+                        for (int i = i0; i < i1; ++i) { const int col = remap(ci[a0 + i]); lo = std::min(lo, col); hi = std::max(hi, col); }
+                    }
+                    if (hi >= 0 && (long long)hi - lo > 65534) { k16 = c; break; }
+                    if (c < 64 && hi >= 0 && hi - lo <= 254) mask |= 1ull << c;
+                }
+                k16_out[b] = k16;
+                if (narrow_mask) narrow_mask[(size_t)b] = mask;
+            }
+        });
+        return DASP_OK;
+    }
+    // gathered columns: the (remapped) ids of the first `cap` nonzeros of every row of `rows`, one row after the other
+    int columns_of_rows(const std::vector<int> &rows, int cap, std::vector<int> &out) const
+    {
+        if (dev) {
+            std::vector<long long> idx;
+            for (int r : rows) for (int j = rp[r], e = std::min(rp[r + 1], rp[r] + cap); j < e; ++j) idx.push_back(j);
+            return devpack_gather_columns(p, *dev, &idx, 0, 0, 0, out);
+        }
+        out.clear();
+        for (int r : rows) for (int j = rp[r], e = std::min(rp[r + 1], rp[r] + cap); j < e; ++j) out.push_back(remap(ci[j]));
+        return DASP_OK;
+    }
+    // ... and of every stride-th nonzero of the matrix
+    int columns_strided(long long stride, std::vector<int> &out) const
+    {
+        if (dev) return devpack_gather_columns(p, *dev, nullptr, 0, stride, (p.nnz + stride - 1) / stride, out);
+        out.clear();
+        for (long long j = 0; j < p.nnz; j += stride) out.push_back(remap(ci[j]));
+        return DASP_OK;
+    }
+};
 }  // namespace
 
 // default longest slab-stored medium row (rowlen_probe: blocks reach the slabs' efficiency only past these lengths)
 constexpr int kSlabDefaultF64 = 16, kSlabDefaultF16 = 24;
 
-enum BuildMode { kTop = 0, kMetaOnly = 1, kPanel = 2 };   // whole plan (may choose column panels) / order+stats only / one panel
 
 template <class T> static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int P, const DevCsr *dev);
-static int decide_panels(const Plan &p, const int *rp, const int *ci, const Remap &remap, const DevCsr *dev, int *scattered = nullptr);
+static int decide_panels(const Plan &p, const CsrProbe &probe, int *scattered = nullptr);
 
 // ---- the REFERENCE's geometry on the same input (VERDICT r3 missing #5).  The native tiles are 16 x K on 64-lane waves, so the padded sizes
 // this library stores differ from the ones the CUDA reference computes (8-row blocks, 8 x 4 tiles, 32-lane warps) -- and a CSV row written
@@ -231,181 +353,257 @@ static RefGeometry reference_geometry(bool f16, int m, int n, int nnz, int n1, i
     return g;
 }
 
-template <class T>
-static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const DevCsr *dev, BuildMode mode = kTop)
-{
+namespace {
+// the stage timer of one build: with DASP_VERBOSE set, lap(what) prints the time since the last lap under the format it was given
+struct LapTimer {
     using clk = std::chrono::steady_clock;
-    const auto t_begin = clk::now();
+    const char *fmt;
+    const clk::time_point t_begin = clk::now();
     const bool verbose = std::getenv("DASP_VERBOSE") != nullptr;
-    auto tick = t_begin;
-    auto lap = [&](const char *what) { if (verbose) { auto now = clk::now(); std::fprintf(stderr, "[dasp plan] %-28s %.3f s\n", what, std::chrono::duration<double>(now - tick).count()); tick = now; } };
-    const Geometry geo = p.geo;
-    const int m = p.m, nnz = p.nnz;
-    const int threads = resolve_threads(p.opt.host_threads);
-    const bool f16 = p.precision == 16;
-    const int block_longest = p.opt.block_longest;
-    const double threshold = p.opt.threshold;
+    clk::time_point tick = t_begin;
+    explicit LapTimer(const char *f) : fmt(f) {}
+    void operator()(const char *what) { if (verbose) { auto now = clk::now(); std::fprintf(stderr, fmt, what, std::chrono::duration<double>(now - tick).count()); tick = now; } }
+    double ms() const { return std::chrono::duration<double, std::milli>(clk::now() - t_begin).count(); }
+};
+
+// ---- the state of one build of the DASP form: what its stages (run_stages) read and hand on.  Every member names ONE quantity; the comment says which stage
+// writes it.  The stages take local copies of what their inner loops read.
+template <class T> struct Build {
+    // inputs, fixed at construction -- except that sort_columns (whole plans only) may point ci, val and dev at sorted copies
+    Plan &p;
+    const int *rp, *ci;
+    const T *val;
+    const DevCsr *dev;                     // the CSR lives on the device: ci and val are not read, the probes and the packing run there
+    const Geometry geo;
+    const int m, nnz, threads;
+    const bool f16;
+    const bool meta_only;                  // order_rid and the classifier counters only (the parent of column panels, a two-phase plan)
+    const bool pack;                       // the nnz-sized arrays are written here (else: on the device / by the panels)
+    const bool natural, mapped;            // y in row order; ... through dst_map (a panel writing into its parent's slot order)
     Remap remap;
-    remap.n_parts = p.opt.n_parts; remap.stride = p.opt.part_stride; remap.b = p.part_bounds.data();
-    const bool meta_only = mode == kMetaOnly;
-    const bool pack = !dev && !meta_only;          // the nnz-sized arrays are written here (else: on the device / by the panels)
+    LapTimer lap{"[dasp plan] %-28s %.3f s\n"};
+
+    // classify_rows: the rows of 1 / 2 / 3 / 4 / 0 nonzeros, in scan order
+    std::vector<int> rid1, rid2, rid3, rid4, rid0;
+    int n1 = 0, n3 = 0;                    // classify_rows: rows of 1 / 3 nonzeros LEFT after the 1&3 pairing (n1_all, n3_all: before it; c13: paired)
+    int n2 = 0, n4 = 0, nz0 = 0, n1_all = 0, n3_all = 0, c13 = 0;      // classify_rows
+    int row_long = 0;                      // classify_rows: rows the classifier called long (the reference's row_long)
+    int row_block = 0;                     // classify_rows: ALL medium rows (the reference's row_block)
+    int nnz_short = 0;                     // classify_rows: nonzeros of the rows of 1..4
+    long long nnz_long = 0;                // classify_rows: nonzeros of the row_long rows
+    // the rows stored as pieces, in slot order.  classify_rows: the row_long rows; medium_rows_as_pieces appends nsp medium rows
+    std::vector<int> ridL;
+    // the medium rows stored as MFMA blocks, in scan order.  classify_rows: all row_block medium rows; assign_slots drops the slab rows;
+    // medium_rows_as_pieces drops the piece rows
+    raw_vector<int> ridM_in;
+    // the same rows and their lengths in packing order.  sort_medium_by_length: all medium rows, by length (descending, stable); assign_slots cuts the slab
+    // rows off the end; decide_windows may swap in the windowed order; medium_rows_as_pieces cuts the piece rows off the front
+    raw_vector<int> ridM, lenM;
+    RefGeometry refg;                      // measure_reference
+    int mfma_rows = 0;                     // assign_slots: medium rows stored as MFMA blocks (row_block less the slab rows); medium_rows_as_pieces takes nsp off
+    std::vector<std::vector<int>> slab_rows;                    // assign_slots: [L] = the medium rows of L nonzeros stored as a slab
+    const std::vector<int> *glist[kNumShortGroups] = {};        // assign_slots: the row list of every short group (rid1 .. rid0, slab_rows[5 ..])
+    double window_frac = 0.0;              // decide_windows: share of the windows' nonzeros inside staged spans
+    int nsp = 0;                           // medium_rows_as_pieces: medium rows stored as pieces
+    int rows_as_pieces = 0;                // medium_rows_as_pieces: rows STORED as pieces = row_long + nsp = ridL.size()
+    std::vector<long long> startL;         // pack_long: first element of every row of ridL in the long segment (+ the total)
+    int nb = 0;                            // split_medium_chunks: MFMA blocks
+    long long n_reg = 0;                   // split_medium_chunks: elements of the regular chunks (padded)
+    int nnz_irreg = 0;                     // split_medium_chunks: elements of the irregular tails
+
+    Build(Plan &p_, const int *rp_, const int *ci_, const T *val_, const DevCsr *dev_, bool meta_only_)
+        : p(p_), rp(rp_), ci(ci_), val(val_), dev(dev_), geo(p_.geo), m(p_.m), nnz(p_.nnz), threads(resolve_threads(p_.opt.host_threads)), f16(p_.precision == 16),
+          meta_only(meta_only_), pack(!dev_ && !meta_only_), natural(p_.opt.y_order == DASP_Y_NATURAL), mapped(natural && !p_.dst_map.empty())
+    {
+        remap.n_parts = p.opt.n_parts; remap.stride = p.opt.part_stride; remap.b = p.part_bounds.data();
+    }
+    Build(const Build &) = delete;         // (glist points into this object)
+    Build &operator=(const Build &) = delete;
+    CsrProbe probe() const { return CsrProbe{p, rp, ci, dev, remap, threads}; }
+    int rowdst(int row) const { return mapped ? p.dst_map[row] : row; }
+    int ydst(int slot) const { return natural ? rowdst(p.order[slot]) : slot; }      // where the row of an order_rid slot writes its y
+};
+
+bool row_ptr_ends_ok(const int *rp, int m, int nnz)
+{
+    if (rp[0] != 0 || rp[m] != nnz) { set_error("csrRowPtr[0] != 0 or csrRowPtr[rowA] != nnzA"); return false; }
+    return true;
+}
+}  // namespace
 
     // ---- validate CSR (the reference trusts its input; an out-of-range column here would be a
     // wild device read, so it is an argument error instead)
-    if (rp[0] != 0 || rp[m] != nnz) { set_error("csrRowPtr[0] != 0 or csrRowPtr[rowA] != nnzA"); return DASP_ERR_ARG; }
-    if (mode == kTop) {
-        std::atomic<int> bad{0};
-        parallel_for(m, threads, 1 << 16, [&](long long b, long long e) {
-            for (long long i = b; i < e; ++i) if (rp[i + 1] < rp[i]) { bad = 1; return; }
-        });
-        const int ncol = p.n;
-        if (dev) { if (!bad) { const int rc = devpack_validate(p, *dev); if (rc == DASP_ERR_ARG) bad = 2; else if (rc != DASP_OK) return rc; } }   // a HIP failure is not "bad column"
-        else parallel_for(nnz, threads, 1 << 18, [&](long long b, long long e) {
-            for (long long i = b; i < e; ++i) if ((unsigned)ci[i] >= (unsigned)ncol) { bad = 2; return; }
-        });
-        if (bad) { set_error(bad == 1 ? "csrRowPtr not monotone" : "column index out of range"); return DASP_ERR_ARG; }
-    }
+template <class T> static int validate_csr(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const int *rp = bld.rp, *ci = bld.ci;
+    const DevCsr *dev = bld.dev;
+    const int m = bld.m, nnz = bld.nnz, threads = bld.threads;
+    if (!row_ptr_ends_ok(rp, m, nnz)) return DASP_ERR_ARG;
+    std::atomic<int> bad{0};
+    parallel_for(m, threads, 1 << 16, [&](long long b, long long e) {
+        for (long long i = b; i < e; ++i) if (rp[i + 1] < rp[i]) { bad = 1; return; }
+    });
+    const int ncol = p.n;
+    if (dev) { if (!bad) { const int rc = devpack_validate(p, *dev); if (rc == DASP_ERR_ARG) bad = 2; else if (rc != DASP_OK) return rc; } }   // a HIP failure is not "bad column"
+    else parallel_for(nnz, threads, 1 << 18, [&](long long b, long long e) {
+        for (long long i = b; i < e; ++i) if ((unsigned)ci[i] >= (unsigned)ncol) { bad = 2; return; }
+    });
+    if (bad) { set_error(bad == 1 ? "csrRowPtr not monotone" : "column index out of range"); return DASP_ERR_ARG; }
+    bld.lap("validate");
+    return DASP_OK;
+}
 
-    lap("validate");
     // opt.sort_columns: rows whose columns do not ascend get their (column, value) pairs sorted by column (stable) -- copies; the caller's arrays stay as they are
-    raw_vector<int> ci_sorted;
-    raw_vector<T> val_sorted;
-    raw_vector<uint32_t> src_sorted;        // value map: the caller's nonzero (+1) at every position of the sorted CSR
-    struct MapSrcReset { Plan &q; bool on; ~MapSrcReset() { if (on) q.map_src = nullptr; } } map_src_reset{p, mode == kTop};      // map_src never outlives the top-level build
-    DevCsr dev_sorted{nullptr, nullptr, nullptr};
-    std::vector<std::shared_ptr<void>> sort_keep;
-    if (mode == kTop && p.opt.sort_columns > 0 && nnz > 0) {
-        if (dev) {
-            int did = 0;
-            if (int rc = devpack_sort_columns(p, *dev, sort_keep, &dev_sorted, &did)) return rc;
-            if (did) dev = &dev_sorted;
-        } else {
-            std::atomic<int> unsorted{0};
-            parallel_for(m, threads, 1 << 14, [&](long long b, long long e) {
-                for (long long i = b; i < e && !unsorted; ++i)
-                    for (int j = rp[i] + 1; j < rp[i + 1]; ++j) if (ci[j] < ci[j - 1]) { unsorted = 1; break; }
+template <class T> struct SortedCsr {
+    raw_vector<int> ci;
+    raw_vector<T> val;
+    raw_vector<uint32_t> src;        // value map: the caller's nonzero (+1) at every position of the sorted CSR
+    DevCsr dev{nullptr, nullptr, nullptr};
+    std::vector<std::shared_ptr<void>> keep;
+};
+template <class T> static int sort_columns(Build<T> &bld, SortedCsr<T> &sorted)
+{
+    Plan &p = bld.p;
+    const int *rp = bld.rp;
+    const int *&ci = bld.ci;
+    const T *&val = bld.val;
+    const DevCsr *&dev = bld.dev;
+    const int m = bld.m, nnz = bld.nnz, threads = bld.threads;
+    if (p.opt.sort_columns <= 0 || nnz <= 0) return DASP_OK;
+    if (dev) {
+        int did = 0;
+        if (int rc = devpack_sort_columns(p, *dev, sorted.keep, &sorted.dev, &did)) return rc;
+        if (did) dev = &sorted.dev;
+    } else {
+        std::atomic<int> unsorted{0};
+        parallel_for(m, threads, 1 << 14, [&](long long b, long long e) {
+            for (long long i = b; i < e && !unsorted; ++i)
+                for (int j = rp[i] + 1; j < rp[i + 1]; ++j) if (ci[j] < ci[j - 1]) { unsorted = 1; break; }
+        });
+        if (unsorted) {
+            sorted.ci.resize((size_t)nnz); sorted.val.resize((size_t)nnz);
+            if (p.value_map) sorted.src.resize((size_t)nnz);      // the map follows each value to its new position
+            parallel_for(m, threads, 1 << 12, [&](long long b, long long e) {
+                struct Entry { int c; T v; uint32_t s; };
+                std::vector<Entry> row;
+                for (long long i = b; i < e; ++i) {
+                    const int a0 = rp[i], a1 = rp[i + 1];
+                    bool ok = true;
+                    for (int j = a0 + 1; j < a1; ++j) if (ci[j] < ci[j - 1]) { ok = false; break; }
+                    if (ok) {
+                        for (int j = a0; j < a1; ++j) { sorted.ci[(size_t)j] = ci[j]; sorted.val[(size_t)j] = val[j]; }
+                        if (p.value_map) for (int j = a0; j < a1; ++j) sorted.src[(size_t)j] = (uint32_t)j + 1u;
+                        continue;
+                    }
+                    row.resize((size_t)(a1 - a0));
+                    for (int j = a0; j < a1; ++j) row[(size_t)(j - a0)] = {ci[j], val[j], (uint32_t)j + 1u};
+                    std::stable_sort(row.begin(), row.end(), [](const Entry &x, const Entry &y) { return x.c < y.c; });
+                    for (int j = a0; j < a1; ++j) { const Entry &q = row[(size_t)(j - a0)]; sorted.ci[(size_t)j] = q.c; sorted.val[(size_t)j] = q.v; }
+                    if (p.value_map) for (int j = a0; j < a1; ++j) sorted.src[(size_t)j] = row[(size_t)(j - a0)].s;
+                }
             });
-            if (unsorted) {
-                ci_sorted.resize((size_t)nnz); val_sorted.resize((size_t)nnz);
-                if (p.value_map) src_sorted.resize((size_t)nnz);      // the map follows each value to its new position
-                parallel_for(m, threads, 1 << 12, [&](long long b, long long e) {
-                    struct Entry { int c; T v; uint32_t s; };
-                    std::vector<Entry> row;
-                    for (long long i = b; i < e; ++i) {
-                        const int a0 = rp[i], a1 = rp[i + 1];
-                        bool ok = true;
-                        for (int j = a0 + 1; j < a1; ++j) if (ci[j] < ci[j - 1]) { ok = false; break; }
-                        if (ok) {
-                            for (int j = a0; j < a1; ++j) { ci_sorted[(size_t)j] = ci[j]; val_sorted[(size_t)j] = val[j]; }
-                            if (p.value_map) for (int j = a0; j < a1; ++j) src_sorted[(size_t)j] = (uint32_t)j + 1u;
-                            continue;
-                        }
-                        row.resize((size_t)(a1 - a0));
-                        for (int j = a0; j < a1; ++j) row[(size_t)(j - a0)] = {ci[j], val[j], (uint32_t)j + 1u};
-                        std::stable_sort(row.begin(), row.end(), [](const Entry &x, const Entry &y) { return x.c < y.c; });
-                        for (int j = a0; j < a1; ++j) { const Entry &q = row[(size_t)(j - a0)]; ci_sorted[(size_t)j] = q.c; val_sorted[(size_t)j] = q.v; }
-                        if (p.value_map) for (int j = a0; j < a1; ++j) src_sorted[(size_t)j] = row[(size_t)(j - a0)].s;
-                    }
-                });
-                ci = ci_sorted.data(); val = val_sorted.data();
-                if (p.value_map) p.map_src = src_sorted.data();
-            }
+            ci = sorted.ci.data(); val = sorted.val.data();
+            if (p.value_map) p.map_src = sorted.src.data();
         }
-        lap("sort columns");
     }
-    if (mode == kTop) {
-        int scattered = 0;
-        const int P = decide_panels(p, rp, ci, remap, dev, &scattered);
-        if (P < 0) return P;
-        if (decide_two_phase(p, rp, scattered)) {
-            // the two-phase (gather-free) form: order_rid and the classifier counters of the whole matrix (row lengths only), then the tile streams
-            if (int rc = build_impl<T>(p, rp, ci, val, nullptr, kMetaOnly)) return rc;
-            lap("whole-matrix meta");
-            // the hybrid (r6): hub rows -- the rule of the column-blocked long rows, decide_long_cb -- leave the two-phase streams for
-            // Plan::lcb (x staged in LDS per column block, no atomics on one LDS word per hub row); everything else stays two-phase
-            auto lcb_counters = [&] {
-                const LongCB &L = p.lcb;
-                dasp_stats_t &s = p.stats;
-                s.lcb_rows = L.n_rows(); s.lcb_elems = (long long)L.elems; s.lcb_col_block = L.cb; s.lcb_units = L.n_units();
-                s.n_workgroups += L.n_units() + ceil_div(L.n_rows(), kWavesPerWG);
-                s.data_X += (long long)L.elems * (geo.vbytes + 2) + (long long)L.n_units() * (long long)std::min(L.cb, p.n) * geo.vbytes;
-            };
-            auto hub_rows = [&](std::vector<unsigned char> &in_lcb, std::vector<int> &slot_of_row) -> bool {
-                p.lcb = LongCB{};
-                if (decide_long_cb(p, rp, 2, in_lcb, 4, 128) <= 0) return false;
-                if (p.opt.y_order != DASP_Y_NATURAL) { slot_of_row.resize((size_t)m); for (int i = 0; i < m; ++i) slot_of_row[(size_t)p.order[(size_t)i]] = i; }
-                return true;
-            };
-            auto hybrid_then_tp = [&](const int *hci, const T *hval) -> int {
-                std::vector<unsigned char> in_lcb;
-                std::vector<int> slot_of_row;
-                if (hub_rows(in_lcb, slot_of_row)) {
-                    const int rc_l = build_long_cb(p, rp, hci, hval, in_lcb, slot_of_row.empty() ? nullptr : slot_of_row.data());
-                    if (rc_l == 1) in_lcb.clear();
-                    else if (rc_l) return rc_l;
-                    lap("hub rows by column block");
-                }
-                const int rc_t = build_two_phase(p, rp, hci, hval, in_lcb.empty() ? nullptr : in_lcb.data());
-                if (rc_t != DASP_OK) { p.lcb = LongCB{}; return rc_t; }
-                if (!in_lcb.empty()) lcb_counters();
-                return DASP_OK;
-            };
-            // the same from a device CSR (r8): the hub rows' pieces and the tiles are counted, ranked and written by devpack.hip, the rules and tables are the host's
-            // (build_long_cb_device, build_two_phase_device); nothing nnz-sized crosses to the host.  kDevNoScratch: the packers' scratch did not fit -- nothing is left behind
-            auto hybrid_then_tp_device = [&]() -> int {
-                std::vector<unsigned char> in_lcb;
-                std::vector<int> slot_of_row;
-                DevTiles pieces, tiles;
-                if (hub_rows(in_lcb, slot_of_row)) {
-                    const int rc_l = build_long_cb_device(p, rp, *dev, in_lcb, slot_of_row.empty() ? nullptr : slot_of_row.data(), pieces);
-                    if (rc_l == 1) in_lcb.clear();
-                    else if (rc_l) return rc_l;
-                    lap("hub rows by column block (device)");
-                }
-                std::vector<long long> off2, off1;
-                int rc_t = build_two_phase_device(p, rp, *dev, in_lcb.empty() ? nullptr : in_lcb.data(), tiles, off2, off1);
-                lap("two-phase tiles (device)");
-                if (rc_t == DASP_OK) {
-                    if (!in_lcb.empty()) lcb_counters();
-                    rc_t = devpack_finish_two_phase(p, *dev, tiles, off2, off1, pieces);
-                    lap("two-phase streams (device)");
-                }
-                if (rc_t != DASP_OK) { release_device(p); p.lcb = LongCB{}; p.tp = TwoPhase{}; p.two_phase = false; p.host_dropped = false; }
-                return rc_t;
-            };
-            int rc2;
-            if (!dev) { rc2 = hybrid_then_tp(ci, val); lap("two-phase streams"); if (rc2 != kTpDeclined) return rc2; }
-            else {
-                rc2 = devpack_forms_enabled() ? hybrid_then_tp_device() : kDevNoScratch;
-                if (rc2 == kDevNoScratch) {
-                    // the fallback (DASP_DEVPACK_FORMS=0, or no room for the packers' scratch): the column ids and values are copied over once, the plan is packed by
-                    // the host packers and uploaded like any host-built plan; Plan::csr_fetch_bytes says so
-                    raw_vector<int> hci((size_t)nnz);
-                    raw_vector<T> hval((size_t)nnz);
-                    raw_vector<uint32_t> hsrc;
-                    if (int rc = devpack_fetch_csr(p, *dev, hci.data(), hval.data())) return rc;
-                    p.csr_fetch_bytes += (long long)nnz * (4 + (long long)sizeof(T));
-                    if (p.value_map && dev->src) {      // a column-sorted device CSR: its map entries travel too (else the host's own index + 1 is the map)
-                        hsrc.resize((size_t)nnz);
-                        if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(hsrc.data()), nullptr)) return rc;
-                        p.csr_fetch_bytes += (long long)nnz * 4;
-                        p.map_src = hsrc.data();
-                    }
-                    rc2 = hybrid_then_tp(hci.data(), hval.data());
-                    p.map_src = nullptr;      // (hsrc ends here)
-                    lap("two-phase streams (device CSR fetched)");
-                    if (rc2 == DASP_OK) return devpack_finish_panels(p);       // a device-built plan comes back uploaded
-                }
-                if (rc2 == DASP_OK) return DASP_OK;
-                if (rc2 != kTpDeclined) return rc2;
-            }
-            // declined by the padding guard (automatic rule only): the matrix keeps its DASP form -- column panels where the rule asked for them, else the plain plan below
-        }
-        if (P >= 2) return build_panels<T>(p, rp, ci, val, P, dev);
+    bld.lap("sort columns");
+    return DASP_OK;
+}
+
+// the hybrid (r6): hub rows -- the rule of the column-blocked long rows, decide_long_cb -- leave the two-phase streams for
+// Plan::lcb (x staged in LDS per column block, no atomics on one LDS word per hub row); everything else stays two-phase
+static void lcb_counters(Plan &p)
+{
+    const LongCB &L = p.lcb;
+    dasp_stats_t &s = p.stats;
+    s.lcb_rows = L.n_rows(); s.lcb_elems = (long long)L.elems; s.lcb_col_block = L.cb; s.lcb_units = L.n_units();
+    s.n_workgroups += L.n_units() + ceil_div(L.n_rows(), kWavesPerWG);
+    s.data_X += (long long)L.elems * (p.geo.vbytes + 2) + (long long)L.n_units() * (long long)std::min(L.cb, p.n) * p.geo.vbytes;
+}
+static bool hub_rows(Plan &p, const int *rp, std::vector<unsigned char> &in_lcb, std::vector<int> &slot_of_row)
+{
+    const int m = p.m;
+    p.lcb = LongCB{};
+    if (decide_long_cb(p, rp, 2, in_lcb, 4, 128) <= 0) return false;
+    if (p.opt.y_order != DASP_Y_NATURAL) { slot_of_row.resize((size_t)m); for (int i = 0; i < m; ++i) slot_of_row[(size_t)p.order[(size_t)i]] = i; }
+    return true;
+}
+template <class T> static int hybrid_then_tp(Build<T> &bld, const int *hci, const T *hval)
+{
+    Plan &p = bld.p;
+    const int *rp = bld.rp;
+    std::vector<unsigned char> in_lcb;
+    std::vector<int> slot_of_row;
+    if (hub_rows(p, rp, in_lcb, slot_of_row)) {
+        const int rc_l = build_long_cb(p, rp, hci, hval, in_lcb, slot_of_row.empty() ? nullptr : slot_of_row.data());
+        if (rc_l == 1) in_lcb.clear();
+        else if (rc_l) return rc_l;
+        bld.lap("hub rows by column block");
     }
-    // ---- classifier: same tests in the same order as dasp_f64.h:499-531.  Two passes over row ranges (count, then fill from the
-    // ranges' prefix sums): every list comes out in row order, exactly what the reference's serial loop produces.
-    int n1 = 0, n2 = 0, n3 = 0, n4 = 0, nz0 = 0, nlong = 0, nmed = 0;
+    const int rc_t = build_two_phase(p, rp, hci, hval, in_lcb.empty() ? nullptr : in_lcb.data());
+    if (rc_t != DASP_OK) { p.lcb = LongCB{}; return rc_t; }
+    if (!in_lcb.empty()) lcb_counters(p);
+    return DASP_OK;
+}
+// the same from a device CSR (r8): the hub rows' pieces and the tiles are counted, ranked and written by devpack.hip, the rules and tables are the host's
+// (build_long_cb_device, build_two_phase_device); nothing nnz-sized crosses to the host.  kDevNoScratch: the packers' scratch did not fit -- nothing is left behind
+template <class T> static int hybrid_then_tp_device(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const int *rp = bld.rp;
+    const DevCsr *dev = bld.dev;
+    std::vector<unsigned char> in_lcb;
+    std::vector<int> slot_of_row;
+    DevTiles pieces, tiles;
+    if (hub_rows(p, rp, in_lcb, slot_of_row)) {
+        const int rc_l = build_long_cb_device(p, rp, *dev, in_lcb, slot_of_row.empty() ? nullptr : slot_of_row.data(), pieces);
+        if (rc_l == 1) in_lcb.clear();
+        else if (rc_l) return rc_l;
+        bld.lap("hub rows by column block (device)");
+    }
+    std::vector<long long> off2, off1;
+    int rc_t = build_two_phase_device(p, rp, *dev, in_lcb.empty() ? nullptr : in_lcb.data(), tiles, off2, off1);
+    bld.lap("two-phase tiles (device)");
+    if (rc_t == DASP_OK) {
+        if (!in_lcb.empty()) lcb_counters(p);
+        rc_t = devpack_finish_two_phase(p, *dev, tiles, off2, off1, pieces);
+        bld.lap("two-phase streams (device)");
+    }
+    if (rc_t != DASP_OK) { release_device(p); p.lcb = LongCB{}; p.tp = TwoPhase{}; p.two_phase = false; p.host_dropped = false; }
+    return rc_t;
+}
+// the fallback (DASP_DEVPACK_FORMS=0, or no room for the packers' scratch): the column ids and values are copied over once, the plan is packed by
+// the host packers and uploaded like any host-built plan; Plan::csr_fetch_bytes says so
+template <class T> static int hybrid_then_tp_fetched(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const DevCsr *dev = bld.dev;
+    const int nnz = bld.nnz;
+    raw_vector<int> hci((size_t)nnz);
+    raw_vector<T> hval((size_t)nnz);
+    raw_vector<uint32_t> hsrc;
+    if (int rc = devpack_fetch_csr(p, *dev, hci.data(), hval.data())) return rc;
+    p.csr_fetch_bytes += (long long)nnz * (4 + (long long)sizeof(T));
+    if (p.value_map && dev->src) {      // a column-sorted device CSR: its map entries travel too (else the host's own index + 1 is the map)
+        hsrc.resize((size_t)nnz);
+        if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(hsrc.data()), nullptr)) return rc;
+        p.csr_fetch_bytes += (long long)nnz * 4;
+        p.map_src = hsrc.data();
+    }
+    const int rc2 = hybrid_then_tp(bld, hci.data(), hval.data());
+    p.map_src = nullptr;      // (hsrc ends here)
+    bld.lap("two-phase streams (device CSR fetched)");
+    return rc2;
+}
+
+// ---- classifier: same tests in the same order as dasp_f64.h:499-531.  Two passes over row ranges (count, then fill from the
+// ranges' prefix sums): every list comes out in row order, exactly what the reference's serial loop produces.
+template <class T> static int classify_rows(Build<T> &bld)
+{
+    const Plan &p = bld.p;
+    const int *rp = bld.rp;
+    const int m = bld.m, threads = bld.threads, block_longest = p.opt.block_longest;
     const int *scan = p.scan_order;      // a column panel: the parent's slot order (Plan::scan_order); everybody else: row order, as the reference's serial loop
     // category of a row: 0 = len 1, 1 = len 3, 2 = len 2, 3 = empty, 4 = len 4, 5 = long, 6 = medium
     auto cat_of = [block_longest](int len) { return len == 1 ? 0 : len == 3 ? 1 : len == 2 ? 2 : len == 0 ? 3 : len == 4 ? 4 : len >= block_longest ? 5 : 6; };
@@ -421,12 +619,14 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         }
     });
     for (int t = 0; t < cparts; ++t) for (int k = 0; k < 7; ++k) ccnt[(size_t)t + 1][(size_t)k] += ccnt[(size_t)t][(size_t)k];     // -> first index of part t
-    n1 = ccnt[(size_t)cparts][0]; n3 = ccnt[(size_t)cparts][1]; n2 = ccnt[(size_t)cparts][2]; nz0 = ccnt[(size_t)cparts][3];
-    n4 = ccnt[(size_t)cparts][4]; nlong = ccnt[(size_t)cparts][5]; nmed = ccnt[(size_t)cparts][6];
-    std::vector<int> rid1(n1), rid2(n2), rid3(n3), rid4(n4), rid0(nz0), ridL(nlong);
-    raw_vector<int> ridM_in((size_t)nmed);       // every element is written by the fill below; no 33 MB zero fill for 8 M rows
+    const std::array<int, 7> &total = ccnt[(size_t)cparts];
+    bld.n1 = total[0]; bld.n3 = total[1]; bld.n2 = total[2]; bld.nz0 = total[3];
+    bld.n4 = total[4]; bld.row_long = total[5]; bld.row_block = total[6];
+    bld.rid1.resize((size_t)bld.n1); bld.rid2.resize((size_t)bld.n2); bld.rid3.resize((size_t)bld.n3); bld.rid4.resize((size_t)bld.n4); bld.rid0.resize((size_t)bld.nz0);
+    bld.ridL.resize((size_t)bld.row_long);
+    bld.ridM_in.resize((size_t)bld.row_block);       // every element is written by the fill below; no 33 MB zero fill for 8 M rows
     {
-        int *const lists[7] = {rid1.data(), rid3.data(), rid2.data(), rid0.data(), rid4.data(), ridL.data(), ridM_in.data()};
+        int *const lists[7] = {bld.rid1.data(), bld.rid3.data(), bld.rid2.data(), bld.rid0.data(), bld.rid4.data(), bld.ridL.data(), bld.ridM_in.data()};
         parallel_for(cparts, cparts, 1, [&](long long t0, long long t1) {
             for (long long t = t0; t < t1; ++t) {
                 std::array<int, 7> at = ccnt[(size_t)t];
@@ -438,31 +638,41 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
             }
         });
     }
-    const int n1_all = n1, n3_all = n3;
-    const int nnz_short = n1 + 3 * n3 + 2 * n2 + 4 * n4;
-    long long nnz_long = 0;
-    for (int r : ridL) nnz_long += rp[r + 1] - rp[r];
+    bld.n1_all = bld.n1; bld.n3_all = bld.n3;
+    bld.nnz_short = bld.n1 + 3 * bld.n3 + 2 * bld.n2 + 4 * bld.n4;
+    bld.nnz_long = 0;
+    for (int r : bld.ridL) bld.nnz_long += rp[r + 1] - rp[r];
 
     // 1&3 pairing count: dasp_f64.h:597-607 (multiple of 8) / dasp_f16.h:1127-1137 (multiple of 32).
     // Kept only because it fixes which slots of the output permutation those rows occupy.
-    int c13 = std::min(n1, n3);
-    if (c13 / 8 >= 16) { c13 = f16 ? 32 * (c13 / 32) : 8 * (c13 / 8); n1 -= c13; n3 -= c13; }
+    int c13 = std::min(bld.n1, bld.n3);
+    if (c13 / 8 >= 16) { c13 = bld.f16 ? 32 * (c13 / 32) : 8 * (c13 / 8); bld.n1 -= c13; bld.n3 -= c13; }
     else c13 = 0;
+    bld.c13 = c13;
 
-    lap("classify");
-    // ---- medium rows sorted by length, descending and stable (what utils.h:118-160,196-203 produce);
-    // lengths are < block_longest, so one counting pass does it.
-    raw_vector<int> ridM((size_t)nmed), lenM((size_t)nmed);
+    bld.lap("classify");
+    return DASP_OK;
+}
+
+// ---- medium rows sorted by length, descending and stable (what utils.h:118-160,196-203 produce);
+// lengths are < block_longest, so one counting pass does it.
+template <class T> static int sort_medium_by_length(Build<T> &bld)
+{
+    const int *rp = bld.rp;
+    const int threads = bld.threads, block_longest = bld.p.opt.block_longest, row_block = bld.row_block;
+    const raw_vector<int> &ridM_in = bld.ridM_in;
+    raw_vector<int> &ridM = bld.ridM, &lenM = bld.lenM;
+    ridM.resize((size_t)row_block); lenM.resize((size_t)row_block);
     {
         // parallel counting sort: per-part histograms, then every (length, part) pair gets its start -- lengths descending, parts in
         // row order inside a length: stable
         const int nbk = std::max(block_longest, 6) + 1;
-        const int sparts = (int)std::max<long long>(1, std::min<long long>(threads, ((long long)nmed + (1 << 16) - 1) >> 16));
+        const int sparts = (int)std::max<long long>(1, std::min<long long>(threads, ((long long)row_block + (1 << 16) - 1) >> 16));
         std::vector<int> hist((size_t)sparts * (size_t)nbk, 0);
         parallel_for(sparts, sparts, 1, [&](long long t0, long long t1) {
             for (long long t = t0; t < t1; ++t) {
                 int *h = hist.data() + (size_t)t * (size_t)nbk;
-                for (long long i = (long long)nmed * t / sparts, e = (long long)nmed * (t + 1) / sparts; i < e; ++i) { const int r = ridM_in[(size_t)i]; h[rp[r + 1] - rp[r]]++; }
+                for (long long i = (long long)row_block * t / sparts, e = (long long)row_block * (t + 1) / sparts; i < e; ++i) { const int r = ridM_in[(size_t)i]; h[rp[r + 1] - rp[r]]++; }
             }
         });
         int run = 0;
@@ -471,7 +681,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         parallel_for(sparts, sparts, 1, [&](long long t0, long long t1) {
             for (long long t = t0; t < t1; ++t) {
                 int *h = hist.data() + (size_t)t * (size_t)nbk;
-                for (long long i = (long long)nmed * t / sparts, e = (long long)nmed * (t + 1) / sparts; i < e; ++i) {
+                for (long long i = (long long)row_block * t / sparts, e = (long long)row_block * (t + 1) / sparts; i < e; ++i) {
                     const int r = ridM_in[(size_t)i], L = rp[r + 1] - rp[r], at = h[L]++;
                     ridM[(size_t)at] = r; lenM[(size_t)at] = L;
                 }
@@ -479,16 +689,85 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         });
     }
 
-    lap("sort medium");
-    RefGeometry refg;
-    {
-        std::vector<int> lenL(ridL.size());
-        for (size_t i = 0; i < ridL.size(); ++i) lenL[i] = rp[ridL[i] + 1] - rp[ridL[i]];
-        refg = reference_geometry(f16, m, p.n, nnz, n1, c13, n3, n4, n2, lenL, lenM, threshold, threads);
+    bld.lap("sort medium");
+    return DASP_OK;
+}
+
+// the reference's padded sizes of this input (reference_geometry above), for the ref_* counters
+template <class T> static int measure_reference(Build<T> &bld)
+{
+    const int *rp = bld.rp;
+    const std::vector<int> &ridL = bld.ridL;
+    std::vector<int> lenL(ridL.size());
+    for (size_t i = 0; i < ridL.size(); ++i) lenL[i] = rp[ridL[i] + 1] - rp[ridL[i]];
+    bld.refg = reference_geometry(bld.f16, bld.m, bld.p.n, bld.nnz, bld.n1, bld.c13, bld.n3, bld.n4, bld.n2, lenL, bld.lenM, bld.p.opt.threshold, bld.threads);
+    bld.lap("reference geometry");
+    return DASP_OK;
+}
+
+// the automatic slab rule of assign_slots (opt.slab_max_len = 0): *pay = the candidates -- the sorted medium rows from first_slab on, short enough for slabs --
+// are better stored as slabs than as MFMA blocks
+template <class T> static int slabs_pay(const Build<T> &bld, int first_slab, bool *pay)
+{
+    const int nnz = bld.nnz, row_block = bld.row_block;
+    const bool f16 = bld.f16;
+    const raw_vector<int> &ridM = bld.ridM, &lenM = bld.lenM;
+    const CsrProbe probe = bld.probe();
+    // auto: a slab lane owns whole rows, so the 64 lanes of a step gather x for 128 / 256 different rows.  That only beats
+    // the blocks when neighbouring rows read neighbouring columns (stencils: the step's gathers coalesce, 8 M rows of 5:
+    // 0.39 -> 0.82 of the roofline); on graph-like rows every lane hits another line and fewer, longer waves lose
+    // (webbase-1M 16.9 -> 22 us, ljournal-2008 0.61 -> 0.70 ms, cop20k_A loses its LDS windows: 11 -> 32 us).
+    // Measure it: pairs of successive equally long candidate rows, share of positions whose columns differ by < 16.
+    std::vector<int> pairs;
+    const int cand = row_block - first_slab, step = std::max(2, (cand / 4096) & ~1);
+    for (int i = first_slab; i + 1 < row_block; i += step)
+        if (lenM[i] == lenM[i + 1]) { pairs.push_back(ridM[i]); pairs.push_back(ridM[i + 1]); }
+    long long near = 0, entries = 0;
+    // "neighbouring": within a 128-byte line of x for f64.  f16 (late r5): within 512 columns -- an f16 tile holds 16 columns of a row, so rows of fewer than 12 have NO regular
+    // chunk at all (a 16 x 16 tile is never 75 % full) and their MFMA blocks are all tail steps: 8 M local rows of 5..8 run at 0.21 of the roofline as blocks, 0.62 as slabs; a
+    // circuit-like mix 0.32 -> 0.60; rows of 17 0.41 -> 0.61 (tools/scratch/circ_probe.py, tools/category_knobs.py).  The graph stand-ins, whose equally long neighbours are far
+    // apart in the matrix, stay blocks (slabs cost webbase-1M f16 15.1 -> 18.8 us, rmat_2M 0.134 -> 0.164 ms: tools/r5_f16_slab_probe.sh)
+    // Only where those degenerate rows are most of the candidates: rows of 12..24 in a band keep their blocks and with them the LDS windows (4.2)
+    long long cand_nnz = 0, tiny_nnz = 0;
+    for (int i = first_slab; i < row_block; ++i) { cand_nnz += lenM[i]; if (lenM[i] < 12) tiny_nnz += lenM[i]; }
+    // r6: ... or where ONE length holds >= 80 % of the candidates' nonzeros (13- / 19-point stencils, fixed-valence meshes in f16): rows of one length keep their
+    // neighbours under the length sort, and as slabs they run half as long again (r5, profiles/r05_category_sweep.md 16: 4 M rows of 17 0.413 -> 0.615 of the roofline,
+    // 3 M rows of 24 0.445 -> 0.666), while thirteen lengths 12..24 -- whose equally long rows lie 13 rows apart -- keep the windows (0.568 against 0.484)
+    long long dom_nnz = 0;
+    for (int i = first_slab; i < row_block; ) { int j = i; while (j < row_block && lenM[j] == lenM[i]) ++j; dom_nnz = std::max(dom_nnz, (long long)(j - i) * lenM[i]); i = j; }
+    // ... whose OWN columns run along lines of x (a slab lane walks its row: consecutive steps then hit the line the last one fetched): under 30 % of a sampled row's
+    // entries on another 128-byte line than their predecessor.  Rows of 12 with columns anywhere within +-500 of the diagonal pass the neighbour test too and LOSE as slabs
+    // (120 k rows, f16: 6.3 us against 4.2 as blocks, gpurun_out/r6/call21.txt)
+    bool dom_runs = false;
+    if (f16 && 5 * dom_nnz >= 4 * cand_nnz && !pairs.empty()) {
+        long long lines = 0, ent = 0;
+        std::vector<int> firsts;
+        for (size_t q = 0; q < pairs.size(); q += 2) firsts.push_back(pairs[q]);
+        if (int rc = probe.line_scatter(firsts, 6, 2147483647, &lines, &ent)) return rc;
+        dom_runs = ent > 0 && 10 * lines < 3 * ent;
     }
-    lap("reference geometry");
-    // ---- output permutation (order_rid): dasp_f64.h:960-976 / dasp_f16.h:1253-1270
-    const int base_s = nlong + nmed;   // (all medium rows: the slab split happens below)
+    const int within = f16 && (2 * tiny_nnz >= cand_nnz || dom_runs) ? 512 : 16;
+    if (int rc = probe.row_coherence(pairs, within, &near, &entries)) return rc;
+    // ... and only when those rows are most of the matrix: a minority of slab waves (128 rows x up to 16 sequential steps) next
+    // to MFMA blocks only lengthens the tail (nlpkkt160's boundary rows: x0.01 5.7 -> 7.9 us, x0.03 15.4 -> 17.4 us)
+    long long slab_nnz = 0;
+    for (int i = first_slab; i < row_block; ++i) slab_nnz += lenM[i];
+    *pay = !(entries == 0 || (double)near < 0.5 * (double)entries || 2 * slab_nnz < (long long)nnz);
+    return DASP_OK;
+}
+
+// ---- output permutation (order_rid): dasp_f64.h:960-976 / dasp_f16.h:1253-1270
+template <class T> static int assign_slots(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const int *rp = bld.rp;
+    const int m = bld.m, threads = bld.threads;
+    const bool f16 = bld.f16;
+    const int n1 = bld.n1, n2 = bld.n2, n3 = bld.n3, n4 = bld.n4, nz0 = bld.nz0, c13 = bld.c13, n1_all = bld.n1_all, n3_all = bld.n3_all;
+    const int row_long = bld.row_long, row_block = bld.row_block;
+    const std::vector<int> &ridL = bld.ridL;
+    raw_vector<int> &ridM = bld.ridM, &lenM = bld.lenM, &ridM_in = bld.ridM_in;
+    const int base_s = row_long + row_block;   // (all medium rows: the slab split happens below)
     const int pg = f16 ? 32 : 8;
     {
         auto linear = [](int count, int base) { SlotMap s{}; s.split = count; s.base[0] = base; s.base[1] = base; return s; };
@@ -510,418 +789,446 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         for (int g = 5; g < kNumShortGroups; ++g) { p.grp[g] = ShortGroup{}; p.grp[g].len = g; }
     }
     // ---- medium rows short enough to be stored as uniform-length slabs instead of MFMA blocks (opt.slab_max_len): the
-    // sorted order puts them last, each length a contiguous run, so a slab's rows keep the slots nlong + position.
+    // sorted order puts them last, each length a contiguous run, so a slab's rows keep the slots row_long + position.
     // Defaults from tools/rowlen_probe.py (8 M rows of one length, fraction of the roofline as blocks / as slabs).
     int slab_max = std::min(kSlabMaxLen, std::max(4, p.opt.slab_max_len > 0 ? p.opt.slab_max_len : (f16 ? kSlabDefaultF16 : kSlabDefaultF64)));
-    const int nmed_all = nmed;
-    int nmf = nmed;
-    while (nmf > 0 && lenM[nmf - 1] <= slab_max) --nmf;               // lenM is sorted descending
-    if (p.opt.slab_max_len <= 0 && nmf < nmed_all && !meta_only) {
-        // auto: a slab lane owns whole rows, so the 64 lanes of a step gather x for 128 / 256 different rows.  That only beats
-        // the blocks when neighbouring rows read neighbouring columns (stencils: the step's gathers coalesce, 8 M rows of 5:
-        // 0.39 -> 0.82 of the roofline); on graph-like rows every lane hits another line and fewer, longer waves lose
-        // (webbase-1M 16.9 -> 22 us, ljournal-2008 0.61 -> 0.70 ms, cop20k_A loses its LDS windows: 11 -> 32 us).
-        // Measure it: pairs of successive equally long candidate rows, share of positions whose columns differ by < 16.
-        std::vector<int> pairs;
-        const int cand = nmed_all - nmf, step = std::max(2, (cand / 4096) & ~1);
-        for (int i = nmf; i + 1 < nmed_all; i += step)
-            if (lenM[i] == lenM[i + 1]) { pairs.push_back(ridM[i]); pairs.push_back(ridM[i + 1]); }
-        long long near = 0, entries = 0;
-        // "neighbouring": within a 128-byte line of x for f64.  f16 (late r5): within 512 columns -- an f16 tile holds 16 columns of a row, so rows of fewer than 12 have NO regular
-        // chunk at all (a 16 x 16 tile is never 75 % full) and their MFMA blocks are all tail steps: 8 M local rows of 5..8 run at 0.21 of the roofline as blocks, 0.62 as slabs; a
-        // circuit-like mix 0.32 -> 0.60; rows of 17 0.41 -> 0.61 (tools/scratch/circ_probe.py, tools/category_knobs.py).  The graph stand-ins, whose equally long neighbours are far
-        // apart in the matrix, stay blocks (slabs cost webbase-1M f16 15.1 -> 18.8 us, rmat_2M 0.134 -> 0.164 ms: tools/r5_f16_slab_probe.sh)
-        // Only where those degenerate rows are most of the candidates: rows of 12..24 in a band keep their blocks and with them the LDS windows (4.2)
-        long long cand_nnz = 0, tiny_nnz = 0;
-        for (int i = nmf; i < nmed_all; ++i) { cand_nnz += lenM[i]; if (lenM[i] < 12) tiny_nnz += lenM[i]; }
-        // r6: ... or where ONE length holds >= 80 % of the candidates' nonzeros (13- / 19-point stencils, fixed-valence meshes in f16): rows of one length keep their
-        // neighbours under the length sort, and as slabs they run half as long again (r5, profiles/r05_category_sweep.md 16: 4 M rows of 17 0.413 -> 0.615 of the roofline,
-        // 3 M rows of 24 0.445 -> 0.666), while thirteen lengths 12..24 -- whose equally long rows lie 13 rows apart -- keep the windows (0.568 against 0.484)
-        long long dom_nnz = 0;
-        for (int i = nmf; i < nmed_all; ) { int j = i; while (j < nmed_all && lenM[j] == lenM[i]) ++j; dom_nnz = std::max(dom_nnz, (long long)(j - i) * lenM[i]); i = j; }
-        // ... whose OWN columns run along lines of x (a slab lane walks its row: consecutive steps then hit the line the last one fetched): under 30 % of a sampled row's
-        // entries on another 128-byte line than their predecessor.  Rows of 12 with columns anywhere within +-500 of the diagonal pass the neighbour test too and LOSE as slabs
-        // (120 k rows, f16: 6.3 us against 4.2 as blocks, gpurun_out/r6/call21.txt)
-        bool dom_runs = false;
-        if (f16 && 5 * dom_nnz >= 4 * cand_nnz && !pairs.empty()) {
-            long long lines = 0, ent = 0;
-            if (dev) { std::vector<int> firsts; for (size_t q = 0; q < pairs.size(); q += 2) firsts.push_back(pairs[q]); if (int rc = devpack_line_scatter(p, *dev, firsts, &lines, &ent)) return rc; }
-            else
-            for (size_t q = 0; q < pairs.size(); q += 2) {
-                const int b = rp[pairs[q]], e = rp[pairs[q] + 1];
-                int prev = remap(ci[b]) >> 6; lines += 1;
-                for (int j = b + 1; j < e; ++j) { const int l = remap(ci[j]) >> 6; lines += l != prev; prev = l; }
-                ent += e - b;
-            }
-            dom_runs = ent > 0 && 10 * lines < 3 * ent;
-        }
-        const int within = f16 && (2 * tiny_nnz >= cand_nnz || dom_runs) ? 512 : 16;
-        if (dev) { if (int rc = devpack_row_coherence(p, *dev, pairs, within, &near, &entries)) return rc; }
-        else
-            for (size_t q = 0; q + 1 < pairs.size(); q += 2) {
-                const int a = rp[pairs[q]], b = rp[pairs[q + 1]], len = rp[pairs[q] + 1] - a;
-                for (int k = 0; k < len; ++k) { const int d = remap(ci[a + k]) - remap(ci[b + k]); near += d > -within && d < within; }
-                entries += len;
-            }
-        // ... and only when those rows are most of the matrix: a minority of slab waves (128 rows x up to 16 sequential steps) next
-        // to MFMA blocks only lengthens the tail (nlpkkt160's boundary rows: x0.01 5.7 -> 7.9 us, x0.03 15.4 -> 17.4 us)
-        long long slab_nnz = 0;
-        for (int i = nmf; i < nmed_all; ++i) slab_nnz += lenM[i];
-        if (entries == 0 || (double)near < 0.5 * (double)entries || 2 * slab_nnz < (long long)nnz) { slab_max = 4; nmf = nmed_all; }
+    int mfma_rows = row_block;
+    while (mfma_rows > 0 && lenM[mfma_rows - 1] <= slab_max) --mfma_rows;               // lenM is sorted descending
+    if (p.opt.slab_max_len <= 0 && mfma_rows < row_block && !bld.meta_only) {
+        bool pay = false;
+        if (int rc = slabs_pay(bld, mfma_rows, &pay)) return rc;
+        if (!pay) { slab_max = 4; mfma_rows = row_block; }
     }
-    std::vector<std::vector<int>> slab_rows((size_t)kSlabMaxLen + 1);
-    for (int i = nmf; i < nmed_all; ) {
+    std::vector<std::vector<int>> &slab_rows = bld.slab_rows;
+    slab_rows.assign((size_t)kSlabMaxLen + 1, std::vector<int>());
+    for (int i = mfma_rows; i < row_block; ) {
         const int L = lenM[i];
         int j = i;
-        while (j < nmed_all && lenM[j] == L) ++j;
+        while (j < row_block && lenM[j] == L) ++j;
         slab_rows[L].assign(ridM.begin() + i, ridM.begin() + j);
         ShortGroup &G = p.grp[L];                                       // group index == row length for L >= 5
-        G.count = j - i; G.map = SlotMap{}; G.map.split = G.count; G.map.base[0] = G.map.base[1] = nlong + i;
+        G.count = j - i; G.map = SlotMap{}; G.map.split = G.count; G.map.base[0] = G.map.base[1] = row_long + i;
         i = j;
     }
-    const std::vector<int> *glist[kNumShortGroups] = {&rid1, &rid2, &rid3, &rid4, &rid0};
+    const std::vector<int> **glist = bld.glist;
+    glist[0] = &bld.rid1; glist[1] = &bld.rid2; glist[2] = &bld.rid3; glist[3] = &bld.rid4; glist[4] = &bld.rid0;
     for (int g = 5; g < kNumShortGroups; ++g) glist[g] = &slab_rows[g];
     p.order.assign((size_t)m, -1);
-    for (int i = 0; i < nlong; ++i) p.order[i] = ridL[i];
-    parallel_for(nmed, threads, 1 << 16, [&](long long b, long long e) { for (long long i = b; i < e; ++i) p.order[(size_t)nlong + (size_t)i] = ridM[(size_t)i]; });
+    for (int i = 0; i < row_long; ++i) p.order[i] = ridL[i];
+    parallel_for(row_block, threads, 1 << 16, [&](long long b, long long e) { for (long long i = b; i < e; ++i) p.order[(size_t)row_long + (size_t)i] = ridM[(size_t)i]; });
     for (int g = 0; g < kNumShortGroups; ++g) {
         const ShortGroup &G = p.grp[g];
         const std::vector<int> &list = *glist[g];
         parallel_for(G.count, threads, 1 << 16, [&](long long b, long long e) { for (long long t = b; t < e; ++t) p.order[(size_t)G.map.slot((int)t)] = list[(size_t)t]; });
     }
     // from here on "medium" means the MFMA part only
-    if (nmf < nmed_all) {
-        ridM.resize((size_t)nmf); lenM.resize((size_t)nmf);
-        raw_vector<int> keep; keep.reserve((size_t)nmf);
+    if (mfma_rows < row_block) {
+        ridM.resize((size_t)mfma_rows); lenM.resize((size_t)mfma_rows);
+        raw_vector<int> keep; keep.reserve((size_t)mfma_rows);
         for (int r : ridM_in) if (rp[r + 1] - rp[r] > slab_max) keep.push_back(r);
         ridM_in.swap(keep);
-        nmed = nmf;
     }
-    const int nlong_cls = nlong;                      // the reference's row_long
-    p.n_mfma_rows = nmf;
-    const bool natural = p.opt.y_order == DASP_Y_NATURAL;
-    const bool mapped = natural && !p.dst_map.empty();     // a panel writing into its parent's slot order
-    auto rowdst = [&](int row) { return mapped ? p.dst_map[row] : row; };
-    auto ydst = [&](int slot) { return natural ? rowdst(p.order[slot]) : slot; };
+    bld.mfma_rows = mfma_rows;
+    p.n_mfma_rows = mfma_rows;
 
-    lap("order_rid");
-    // ---- optional windowed order for the medium rows (LDS-staged x).  The reference sorts all
-    // medium rows globally by length, which scatters the 16 rows of a block over the matrix; here rows are sorted inside
-    // windows of `row_window` consecutive medium rows only, one window per workgroup, so a workgroup's rows share a narrow
-    // span of x that is staged once in LDS.  Output slots stay the reference's (order_rid untouched): y goes through med_dst.
-    p.windowed = false; p.win_hybrid = false; p.win_rel16 = false; p.row_window = 0; p.lds_bytes = 0;
-    p.med_dst.clear(); p.win_cmin.clear(); p.win_len.clear();
-    double window_frac = 0.0;
-    if ((p.opt.x_window >= 0 || p.opt.x_window == -2) && nmed > 0 && !meta_only) {
-        // default window height: every window pays the same x copy whatever its height, so as few windows as still occupy the
-        // 256 CUs -- one workgroup each, or two each (2 x 80 KiB of LDS) once a window would pass 1024 rows.  Just under the
-        // CU count, not at it: sweeps on the cop20k_A stand-in put the optimum at 200-230 windows (162 k medium rows: 318 / 255 /
-        // 231 / 212 / 159 windows = 17.7 / 18.6 / 14.6 / 14.6 / 16.0 us; 130 k: 255 / 226 / 170 = 15.4 / 13.2 / 13.4; 65 k:
-        // 507 / 254 / 127 / 64 = 8.4 / 7.4 / 9.1 / 13.4) and at ~424 for 325 k rows (424 / 318 = 24.6 / 27.3 us).
-        // r6 (profiles/r06_small_matrix.md): with the 128-register build exactly one window workgroup resides per CU, so the fastest grid is the one that puts a
-        // workgroup on EVERY CU and none behind another: windows (rounded up to a whole number per XCD, as the kernel deals them) + long-piece workgroups + short-tile
-        // workgroups (none where the tiles fold into the windows) <= 256.  cop20k_A: 212 windows of 512 rows 10.56 us, 242 of 448 10.08, 251 of 432 WITH seven short-tile
-        // workgroups behind them 17.6 (263 workgroups: seven CUs take a second one) -- hence the count of ALL workgroups, and window heights in whole blocks (16 rows).
-        int R = p.opt.row_window;
-        if (R <= 0) {
-            const int cus = 256, SR = geo.short_rows;
-            int est_tiles = 0;
-            for (int g = 0; g < kNumShortGroups; ++g) est_tiles += ceil_div(p.grp[g].count, SR);
-            long long est_pieces = nlong;
-            for (int i = 0; i < nlong; ++i) est_pieces += (rp[ridL[(size_t)i] + 1] - rp[ridL[(size_t)i]]) / 1024;
-            for (int r = 128; r <= 1024 && R <= 0; r += kMedRows) {
-                const int nWr = ceil_div(nmed, r), wpw_r = std::min(16, r / kMedRows);
-                const int wgs = ceil_div(nWr, 8) * 8 + (int)ceil_div(est_pieces, (long long)wpw_r) + (win_fold_tiles(nWr, est_tiles) ? 0 : ceil_div(est_tiles, wpw_r));
-                if (wgs <= cus) R = r;
+    bld.lap("order_rid");
+    return DASP_OK;
+}
+
+// decide_windows' working set
+struct Windows {
+    int R = 0, nW = 0;                          // rows per window (whole blocks), windows
+    int A = 1;                                  // window base aligned for 16-byte copies
+    int cap_bytes = 0;                          // the largest span a window may stage
+    bool order_only = false;                    // windowed order, no LDS staging (every window gathers from global memory)
+    raw_vector<int> ridW, lenW;                 // order_in_windows: the MFMA medium rows, sorted by length inside each window
+    std::vector<int> wlo, whi;                  // scan_window_spans: column span [lo, hi] of every window (hi < 0: not looked at)
+    std::vector<long long> wnnz;                // scan_window_spans: nonzeros of every window
+    std::vector<int> cmin, wlen;                // fit_windows, hybrid_windows: the staged span of every window (length 0: none)
+    long long fit = 0, all = 0;                 // fit_windows, hybrid_windows: nonzeros inside staged spans / of all windows
+    int maxlen = 0;                             // fit_windows, hybrid_windows: the longest staged span
+};
+
+// default window height: every window pays the same x copy whatever its height, so as few windows as still occupy the
+// 256 CUs -- one workgroup each, or two each (2 x 80 KiB of LDS) once a window would pass 1024 rows.  Just under the
+// CU count, not at it: sweeps on the cop20k_A stand-in put the optimum at 200-230 windows (162 k medium rows: 318 / 255 /
+// 231 / 212 / 159 windows = 17.7 / 18.6 / 14.6 / 14.6 / 16.0 us; 130 k: 255 / 226 / 170 = 15.4 / 13.2 / 13.4; 65 k:
+// 507 / 254 / 127 / 64 = 8.4 / 7.4 / 9.1 / 13.4) and at ~424 for 325 k rows (424 / 318 = 24.6 / 27.3 us).
+// r6 (profiles/r06_small_matrix.md): with the 128-register build exactly one window workgroup resides per CU, so the fastest grid is the one that puts a
+// workgroup on EVERY CU and none behind another: windows (rounded up to a whole number per XCD, as the kernel deals them) + long-piece workgroups + short-tile
+// workgroups (none where the tiles fold into the windows) <= 256.  cop20k_A: 212 windows of 512 rows 10.56 us, 242 of 448 10.08, 251 of 432 WITH seven short-tile
+// workgroups behind them 17.6 (263 workgroups: seven CUs take a second one) -- hence the count of ALL workgroups, and window heights in whole blocks (16 rows).
+template <class T> static int default_row_window(const Build<T> &bld)
+{
+    const Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp;
+    const std::vector<int> &ridL = bld.ridL;
+    const int row_long = bld.row_long, mfma_rows = bld.mfma_rows;
+    int R = p.opt.row_window;
+    if (R <= 0) {
+        const int cus = 256, SR = geo.short_rows;
+        int est_tiles = 0;
+        for (int g = 0; g < kNumShortGroups; ++g) est_tiles += ceil_div(p.grp[g].count, SR);
+        long long est_pieces = row_long;
+        for (int i = 0; i < row_long; ++i) est_pieces += (rp[ridL[(size_t)i] + 1] - rp[ridL[(size_t)i]]) / 1024;
+        for (int r = 128; r <= 1024 && R <= 0; r += kMedRows) {
+            const int nWr = ceil_div(mfma_rows, r), wpw_r = std::min(16, r / kMedRows);
+            const int wgs = ceil_div(nWr, 8) * 8 + (int)ceil_div(est_pieces, (long long)wpw_r) + (win_fold_tiles(nWr, est_tiles) ? 0 : ceil_div(est_tiles, wpw_r));
+            if (wgs <= cus) R = r;
+        }
+        // more rows than 256 windows of 1024 hold: two workgroups per CU (the 64-register build, 2 x 80 KiB of LDS), ~448 windows as before
+        if (R <= 0) R = std::max(128, ceil_div(ceil_div(mfma_rows, 448), 64) * 64);
+    }
+    R = std::min(1024, std::max(64, (R / kMedRows) * kMedRows));         // whole blocks; <= 16 waves per workgroup, 1-4 blocks per wave
+    return R;
+}
+
+// medium rows in row order, then a stable descending length sort inside each window
+template <class T> static void order_in_windows(const Build<T> &bld, Windows &w)
+{
+    const int *rp = bld.rp;
+    const int threads = bld.threads, block_longest = bld.p.opt.block_longest, mfma_rows = bld.mfma_rows, R = w.R;
+    const raw_vector<int> &ridM_in = bld.ridM_in;
+    raw_vector<int> &ridW = w.ridW, &lenW = w.lenW;
+    ridW.resize((size_t)mfma_rows); lenW.resize((size_t)mfma_rows);
+    const raw_vector<int> &rows = ridM_in;             // the medium rows in row order
+    const int nW = ceil_div(mfma_rows, R);
+    parallel_for(nW, threads, 8, [&](long long w0, long long w1) {
+        std::vector<int> bucket;
+        for (long long w = w0; w < w1; ++w) {
+            const int a0 = (int)w * R, a1 = std::min(mfma_rows, a0 + R);
+            bucket.assign((size_t)block_longest + 1, 0);
+            for (int i = a0; i < a1; ++i) bucket[rp[rows[i] + 1] - rp[rows[i]]]++;
+            int run = a0;
+            for (int L = block_longest; L >= 0; --L) { int c = bucket[L]; bucket[L] = run; run += c; }
+            for (int i = a0; i < a1; ++i) { const int L = rp[rows[i] + 1] - rp[rows[i]]; const int at = bucket[L]++; ridW[at] = rows[i]; lenW[at] = L; }
+        }
+    });
+}
+
+// the column span and the nonzeros of every window -- from a sample first, where that can spare the full scan
+template <class T> static int scan_window_spans(const Build<T> &bld, Windows &w)
+{
+    const Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int threads = bld.threads, mfma_rows = bld.mfma_rows, R = w.R, nW = w.nW, A = w.A;
+    const raw_vector<int> &ridW = w.ridW, &lenW = w.lenW;
+    std::vector<int> &wlo = w.wlo, &whi = w.whi;
+    std::vector<long long> &wnnz = w.wnnz;
+    const CsrProbe probe = bld.probe();
+    w.cmin.assign((size_t)nW, 0); w.wlen.assign((size_t)nW, 0);
+    wnnz.assign((size_t)nW, 0); wlo.assign((size_t)nW, 0); whi.assign((size_t)nW, 0);
+    // auto mode on a large matrix: look at 64 evenly spaced windows first.  If under a quarter of THEIR nonzeros sit in windows
+    // that would fit even the whole 160 KiB of LDS, no strict window rule can reach its 50 % -- skip reading every column id of the
+    // matrix for nothing (HV15R: 332 ms of the host path's 659, 6 of the device path's 38)
+    bool scan_all = true;
+    if (p.opt.x_window == 0 && nW > 256) {
+        const int ns = 64;
+        raw_vector<int> sample; sample.reserve((size_t)ns * (size_t)R);
+        for (int q = 0; q < ns; ++q) {
+            const int w = (int)((long long)q * (nW - 1) / ns);                 // never the (possibly partial) last window
+            sample.insert(sample.end(), ridW.begin() + (size_t)w * R, ridW.begin() + (size_t)(w + 1) * R);
+        }
+        std::vector<int> slo(ns), shi(ns);
+        std::vector<long long> snz(ns);
+        if (int rc = probe.window_spans(sample, ns * R, R, slo.data(), shi.data(), snz.data())) return rc;
+        long long fit_s = 0, all_s = 0;
+        for (int q = 0; q < ns; ++q) {
+            all_s += snz[q];
+            if (shi[q] >= 0 && ((long long)shi[q] - (slo[q] / A) * A + 1) * geo.vbytes <= kWinLdsMax) fit_s += snz[q];
+        }
+        scan_all = 4 * fit_s >= all_s;
+    }
+    if (scan_all) { if (int rc = probe.window_spans(ridW, mfma_rows, R, wlo.data(), whi.data(), wnnz.data())) return rc; }
+    else
+        parallel_for(nW, threads, 64, [&](long long w0, long long w1) {
+            for (long long w = w0; w < w1; ++w) {                               // "does not fit": what the full scan would have concluded
+                wlo[(size_t)w] = 2147483647; whi[(size_t)w] = -1;
+                long long k = 0;
+                for (long long i = w * R, e = std::min<long long>(mfma_rows, (w + 1) * R); i < e; ++i) k += lenW[(size_t)i];
+                wnnz[(size_t)w] = k;
             }
-            // more rows than 256 windows of 1024 hold: two workgroups per CU (the 64-register build, 2 x 80 KiB of LDS), ~448 windows as before
-            if (R <= 0) R = std::max(128, ceil_div(ceil_div(nmed, 448), 64) * 64);
-        }
-        R = std::min(1024, std::max(64, (R / kMedRows) * kMedRows));         // whole blocks; <= 16 waves per workgroup, 1-4 blocks per wave
-        // default cap: 80 KiB = two workgroups per CU out of gfx950's 160 KiB of LDS
-        const bool order_only = p.opt.x_window == -2;          // windowed order, no LDS staging (every window gathers from global memory)
-        int cap_bytes = order_only ? 0 : (p.opt.x_window > 0 ? std::min(p.opt.x_window, kWinLdsMax) : 80 * 1024);
-        const int A = 16 / geo.vbytes;                         // window base aligned for 16-byte copies
-        // medium rows in row order, then a stable descending length sort inside each window
-        raw_vector<int> ridW((size_t)nmed), lenW((size_t)nmed);
-        {
-            const raw_vector<int> &rows = ridM_in;             // the medium rows in row order
-            const int nW = ceil_div(nmed, R);
-            parallel_for(nW, threads, 8, [&](long long w0, long long w1) {
-                std::vector<int> bucket;
-                for (long long w = w0; w < w1; ++w) {
-                    const int a0 = (int)w * R, a1 = std::min(nmed, a0 + R);
-                    bucket.assign((size_t)block_longest + 1, 0);
-                    for (int i = a0; i < a1; ++i) bucket[rp[rows[i] + 1] - rp[rows[i]]]++;
-                    int run = a0;
-                    for (int L = block_longest; L >= 0; --L) { int c = bucket[L]; bucket[L] = run; run += c; }
-                    for (int i = a0; i < a1; ++i) { const int L = rp[rows[i] + 1] - rp[rows[i]]; const int at = bucket[L]++; ridW[at] = rows[i]; lenW[at] = L; }
+        });
+    return DASP_OK;
+}
+
+// which windows' whole spans fit cap_bytes of LDS, and the share of the windows' nonzeros inside them (window_frac)
+template <class T> static void fit_windows(Build<T> &bld, Windows &w)
+{
+    const Geometry &geo = bld.geo;
+    const int nW = w.nW, A = w.A, cap_bytes = w.cap_bytes;
+    const std::vector<int> &wlo = w.wlo, &whi = w.whi;
+    const std::vector<long long> &wnnz = w.wnnz;
+    std::vector<int> &cmin = w.cmin, &wlen = w.wlen;
+    long long &fit = w.fit, &all = w.all;
+    int &maxlen = w.maxlen;
+    double &window_frac = bld.window_frac;
+    fit = 0; all = 0; maxlen = 0;
+    for (int w = 0; w < nW; ++w) {
+        const int lo = (wlo[w] / A) * A, hi = whi[w];
+        const long long span = (long long)hi - lo + 1;
+        if (hi >= 0 && span * geo.vbytes <= cap_bytes) { cmin[w] = lo; wlen[w] = (int)span; }
+        else { cmin[w] = 0; wlen[w] = 0; }
+        all += wnnz[w];
+        if (wlen[w] > 0) { fit += wnnz[w]; maxlen = std::max(maxlen, wlen[w]); }
+    }
+    window_frac = all > 0 ? (double)fit / (double)all : 0.0;
+}
+
+// ---- hybrid windows: when the whole span of a window does not fit (graph-like rows: most columns near the rows -- the
+// pages of a host, the members of a community -- plus a scattered remainder), stage the DENSEST span of cap bytes and let
+// the gathers that fall outside it read global memory (kernel: XHyb).  Host CSR only.  It pays on rows of even length whose
+// columns form a band plus outliers (tools/hybrid_probe.py: 2 M rows of 14, +-3000 band + 10 % anywhere, f64 0.234 -> 0.189 ms,
+// f16 0.086 -> 0.061 ms; +-8000 + 3 %: 0.190 -> 0.126 ms); on the power-law stand-ins the window workgroups themselves cost
+// more than the LDS gathers save (webbase-1M 14.6 -> 22.4 us with 85 % of the medium gathers staged, ljournal-2008
+// 0.545 -> 0.587 ms with 53 %: one 1024-thread workgroup per window balances rows of 5..255 nonzeros badly).  So auto
+// asks for even rows (longest <= 4 x the mean) on top of: strict windows cover < half, densest spans cover >= 60 %.
+template <class T> static void hybrid_windows(Build<T> &bld, Windows &w)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp, *ci = bld.ci;
+    const DevCsr *dev = bld.dev;
+    const Remap remap = bld.remap;
+    const int threads = bld.threads, mfma_rows = bld.mfma_rows, R = w.R, nW = w.nW, A = w.A;
+    const bool order_only = w.order_only;
+    const raw_vector<int> &lenM = bld.lenM, &ridW = w.ridW;
+    const std::vector<long long> &wnnz = w.wnnz;
+    std::vector<int> &cmin = w.cmin, &wlen = w.wlen;
+    const long long all = w.all;
+    long long &fit = w.fit;
+    int &maxlen = w.maxlen;
+    double &window_frac = bld.window_frac;
+    p.win_hybrid = false;
+    const bool even_rows = mfma_rows > 0 && (long long)lenM[0] * mfma_rows <= 4 * std::max<long long>(1, all);
+    if (!dev && !order_only && p.opt.x_window_hybrid >= 0 &&
+        (p.opt.x_window_hybrid > 0 || (p.opt.x_window == 0 && window_frac < 0.5 && even_rows))) {
+        const int hcap = p.opt.x_window > 0 ? std::min(p.opt.x_window, kWinLdsMax) : 80 * 1024;    // two workgroups per CU
+        const long long cap_cols = std::max<long long>(A, (hcap / geo.vbytes / A) * A);
+        const long long xl = p.opt.n_parts > 0 ? (long long)p.opt.n_parts * p.opt.part_stride : (long long)p.n;
+        std::vector<int> hmin(nW), hlen(nW);
+        std::vector<long long> hin(nW);
+        const bool force_sort = std::getenv("DASP_HYBRID_SORT") != nullptr;       // test knob: the sort-based search (tests compare the two)
+        // auto mode on a large matrix: the densest spans of 64 evenly spaced windows first -- when they hold under 55 % of those
+        // windows' gathers the whole will not reach 60 %, and sorting every window's columns is skipped (HV15R: 0.33 s of the host
+        // path, its three-plane rows give 33 %; nlpkkt160: 0.45 s, ~50 %)
+        std::vector<int> wlist;
+        if (p.opt.x_window_hybrid == 0 && nW > 256) for (int q = 0; q < 64; ++q) wlist.push_back((int)((long long)q * (nW - 1) / 64));
+        bool sampled = !wlist.empty();
+        for (int pass = sampled ? 0 : 1; pass < 2; ++pass) {
+        if (pass == 1) { wlist.resize((size_t)nW); for (int w = 0; w < nW; ++w) wlist[(size_t)w] = w; }
+        parallel_for((long long)wlist.size(), threads, 4, [&](long long w0, long long w1) {
+            std::vector<int> cols, hist;
+            for (long long wi = w0; wi < w1; ++wi) {
+                const int w = wlist[(size_t)wi];
+                const int a0 = (int)w * R, a1 = std::min(mfma_rows, a0 + R);
+                cols.clear();
+                int cmin_w = 2147483647, cmax_w = -1;
+                for (int i = a0; i < a1; ++i) {
+                    const int r = ridW[i];
+                    for (int j = rp[r]; j < rp[r + 1]; ++j) { const int c = remap(ci[j]); cols.push_back(c); cmin_w = std::min(cmin_w, c); cmax_w = std::max(cmax_w, c); }
                 }
-            });
-        }
-        const int nW = ceil_div(nmed, R);
-        std::vector<int> cmin(nW), wlen(nW);
-        std::vector<long long> wnnz(nW);
-        std::vector<int> wlo(nW), whi(nW);
-        // span [lo, hi] and nonzeros of the windows over rows list[0 .. n): one window per R rows
-        auto spans_of = [&](const raw_vector<int> &list, int n, int *lo_out, int *hi_out, long long *nnz_out) -> int {
-            if (dev) return devpack_window_spans(p, *dev, list, R, lo_out, hi_out, nnz_out);
-            parallel_for(ceil_div(n, R), threads, 8, [&](long long w0, long long w1) {
-                for (long long w = w0; w < w1; ++w) {
-                    const int a0 = (int)w * R, a1 = std::min(n, a0 + R);
-                    int lo = 2147483647, hi = -1; long long k = 0;
-                    for (int i = a0; i < a1; ++i) {
-                        const int r = list[(size_t)i];
-                        for (int j = rp[r]; j < rp[r + 1]; ++j) { const int c = remap(ci[j]); lo = std::min(lo, c); hi = std::max(hi, c); }
-                        k += rp[r + 1] - rp[r];
+                // best 16-byte-aligned start: for every aligned start that holds an entry, the entries in [start, start + cap_cols); the
+                // first start with the largest count wins.  (An entry c that is not the smallest of its aligned group counts fewer entries
+                // than the group's smallest one -- which is itself inside [group start, c) -- so only group starts compete.)
+                long long best = 0; int bs = 0;
+                const long long g0 = cols.empty() ? 0 : cmin_w / A, ngrp = cols.empty() ? 0 : cmax_w / A - g0 + 1;
+                if (!cols.empty() && ngrp <= 4 * (long long)cols.size() + 1024 && !force_sort) {
+                    // dense enough: a histogram over the aligned groups and a sliding sum -- O(entries + groups) instead of a sort
+                    hist.assign((size_t)ngrp + 1, 0);
+                    for (int c : cols) hist[(size_t)(c / A - g0)]++;
+                    const long long wg = cap_cols / A;                                  // groups per span
+                    long long run = 0;
+                    for (long long g = 0; g < std::min(wg, ngrp); ++g) run += hist[(size_t)g];
+                    for (long long g = 0; g < ngrp; ++g) {
+                        if (hist[(size_t)g] > 0 && run > best) { best = run; bs = (int)((g0 + g) * A); }
+                        run -= hist[(size_t)g];
+                        if (g + wg < ngrp) run += hist[(size_t)(g + wg)];
                     }
-                    lo_out[w] = lo; hi_out[w] = hi; nnz_out[w] = k;
+                } else {
+                std::sort(cols.begin(), cols.end());
+                size_t hi_i = 0;
+                for (size_t lo_i = 0; lo_i < cols.size(); ++lo_i) {
+                    if (lo_i && cols[lo_i] == cols[lo_i - 1]) continue;
+                    const long long st = (cols[lo_i] / A) * A;
+                    if (hi_i < lo_i) hi_i = lo_i;
+                    while (hi_i < cols.size() && cols[hi_i] < st + cap_cols) ++hi_i;
+                    // entries between the aligned start and cols[lo_i] belong to the span too, but they are < A away: ignore them
+                    const long long cnt = (long long)(hi_i - lo_i);
+                    if (cnt > best) { best = cnt; bs = (int)st; }
                 }
-            });
-            return DASP_OK;
-        };
-        // auto mode on a large matrix: look at 64 evenly spaced windows first.  If under a quarter of THEIR nonzeros sit in windows
-        // that would fit even the whole 160 KiB of LDS, no strict window rule can reach its 50 % -- skip reading every column id of the
-        // matrix for nothing (HV15R: 332 ms of the host path's 659, 6 of the device path's 38)
-        bool scan_all = true;
-        if (p.opt.x_window == 0 && nW > 256) {
-            const int ns = 64;
-            raw_vector<int> sample; sample.reserve((size_t)ns * (size_t)R);
-            for (int q = 0; q < ns; ++q) {
-                const int w = (int)((long long)q * (nW - 1) / ns);                 // never the (possibly partial) last window
-                sample.insert(sample.end(), ridW.begin() + (size_t)w * R, ridW.begin() + (size_t)(w + 1) * R);
+                }
+                hmin[w] = bs; hin[w] = best;
+                hlen[w] = (int)std::min<long long>(cap_cols, xl - bs);
             }
-            std::vector<int> slo(ns), shi(ns);
-            std::vector<long long> snz(ns);
-            if (int rc = spans_of(sample, ns * R, slo.data(), shi.data(), snz.data())) return rc;
-            long long fit_s = 0, all_s = 0;
-            for (int q = 0; q < ns; ++q) {
-                all_s += snz[q];
-                if (shi[q] >= 0 && ((long long)shi[q] - (slo[q] / A) * A + 1) * geo.vbytes <= kWinLdsMax) fit_s += snz[q];
-            }
-            scan_all = 4 * fit_s >= all_s;
+        });
+        if (pass == 0) {
+            long long in_s = 0, all_s = 0;
+            for (int w : wlist) { in_s += hin[(size_t)w]; all_s += wnnz[(size_t)w]; }
+            if (100 * in_s < 55 * all_s) { std::fill(hin.begin(), hin.end(), 0); break; }     // cover stays 0: no hybrid windows
         }
-        if (scan_all) { if (int rc = spans_of(ridW, nmed, wlo.data(), whi.data(), wnnz.data())) return rc; }
-        else
-            parallel_for(nW, threads, 64, [&](long long w0, long long w1) {
-                for (long long w = w0; w < w1; ++w) {                               // "does not fit": what the full scan would have concluded
-                    wlo[(size_t)w] = 2147483647; whi[(size_t)w] = -1;
-                    long long k = 0;
-                    for (long long i = w * R, e = std::min<long long>(nmed, (w + 1) * R); i < e; ++i) k += lenW[(size_t)i];
-                    wnnz[(size_t)w] = k;
-                }
-            });
-        long long fit = 0, all = 0; int maxlen = 0;
-        auto fit_windows = [&]() {
-            fit = 0; all = 0; maxlen = 0;
+        }
+        long long in = 0;
+        for (int w = 0; w < nW; ++w) in += hin[w];
+        const double cover = all > 0 ? (double)in / (double)all : 0.0;
+        if (p.opt.x_window_hybrid > 0 || cover >= 0.6) {
+            p.win_hybrid = true;
+            fit = 0; maxlen = 0;
             for (int w = 0; w < nW; ++w) {
-                const int lo = (wlo[w] / A) * A, hi = whi[w];
-                const long long span = (long long)hi - lo + 1;
-                if (hi >= 0 && span * geo.vbytes <= cap_bytes) { cmin[w] = lo; wlen[w] = (int)span; }
-                else { cmin[w] = 0; wlen[w] = 0; }
-                all += wnnz[w];
-                if (wlen[w] > 0) { fit += wnnz[w]; maxlen = std::max(maxlen, wlen[w]); }
+                // a window whose best span holds under a quarter of its gathers is not worth its copy: global gathers only
+                if (hin[w] * 4 < wnnz[w] || hlen[w] <= 0) { cmin[w] = 0; wlen[w] = 0; continue; }
+                cmin[w] = hmin[w]; wlen[w] = hlen[w]; fit += hin[w]; maxlen = std::max(maxlen, wlen[w]);
             }
             window_frac = all > 0 ? (double)fit / (double)all : 0.0;
-        };
-        fit_windows();
-        // auto: when the spans are too wide for two workgroups per CU (80 KiB each), one workgroup per CU with all of the LDS
-        // still beats global gathers on band-scattered rows (+-30 k columns, f16: 98.8 -> 65.9 us; +-8 k, f64: 166.8 -> 115.8 us)
-        if (p.opt.x_window == 0 && window_frac < 0.5) { cap_bytes = kWinLdsMax; fit_windows(); }
-        const bool force = p.opt.x_window > 0;
-        // ---- hybrid windows: when the whole span of a window does not fit (graph-like rows: most columns near the rows -- the
-        // pages of a host, the members of a community -- plus a scattered remainder), stage the DENSEST span of cap bytes and let
-        // the gathers that fall outside it read global memory (kernel: XHyb).  Host CSR only.  It pays on rows of even length whose
-        // columns form a band plus outliers (tools/hybrid_probe.py: 2 M rows of 14, +-3000 band + 10 % anywhere, f64 0.234 -> 0.189 ms,
-        // f16 0.086 -> 0.061 ms; +-8000 + 3 %: 0.190 -> 0.126 ms); on the power-law stand-ins the window workgroups themselves cost
-        // more than the LDS gathers save (webbase-1M 14.6 -> 22.4 us with 85 % of the medium gathers staged, ljournal-2008
-        // 0.545 -> 0.587 ms with 53 %: one 1024-thread workgroup per window balances rows of 5..255 nonzeros badly).  So auto
-        // asks for even rows (longest <= 4 x the mean) on top of: strict windows cover < half, densest spans cover >= 60 %.
-        p.win_hybrid = false;
-        const bool even_rows = nmed > 0 && (long long)lenM[0] * nmed <= 4 * std::max<long long>(1, all);
-        if (!dev && !order_only && p.opt.x_window_hybrid >= 0 &&
-            (p.opt.x_window_hybrid > 0 || (p.opt.x_window == 0 && window_frac < 0.5 && even_rows))) {
-            const int hcap = p.opt.x_window > 0 ? std::min(p.opt.x_window, kWinLdsMax) : 80 * 1024;    // two workgroups per CU
-            const long long cap_cols = std::max<long long>(A, (hcap / geo.vbytes / A) * A);
-            const long long xl = p.opt.n_parts > 0 ? (long long)p.opt.n_parts * p.opt.part_stride : (long long)p.n;
-            std::vector<int> hmin(nW), hlen(nW);
-            std::vector<long long> hin(nW);
-            const bool force_sort = std::getenv("DASP_HYBRID_SORT") != nullptr;       // test knob: the sort-based search (tests compare the two)
-            // auto mode on a large matrix: the densest spans of 64 evenly spaced windows first -- when they hold under 55 % of those
-            // windows' gathers the whole will not reach 60 %, and sorting every window's columns is skipped (HV15R: 0.33 s of the host
-            // path, its three-plane rows give 33 %; nlpkkt160: 0.45 s, ~50 %)
-            std::vector<int> wlist;
-            if (p.opt.x_window_hybrid == 0 && nW > 256) for (int q = 0; q < 64; ++q) wlist.push_back((int)((long long)q * (nW - 1) / 64));
-            bool sampled = !wlist.empty();
-            for (int pass = sampled ? 0 : 1; pass < 2; ++pass) {
-            if (pass == 1) { wlist.resize((size_t)nW); for (int w = 0; w < nW; ++w) wlist[(size_t)w] = w; }
-            parallel_for((long long)wlist.size(), threads, 4, [&](long long w0, long long w1) {
-                std::vector<int> cols, hist;
-                for (long long wi = w0; wi < w1; ++wi) {
-                    const int w = wlist[(size_t)wi];
-                    const int a0 = (int)w * R, a1 = std::min(nmed, a0 + R);
-                    cols.clear();
-                    int cmin_w = 2147483647, cmax_w = -1;
-                    for (int i = a0; i < a1; ++i) {
-                        const int r = ridW[i];
-                        for (int j = rp[r]; j < rp[r + 1]; ++j) { const int c = remap(ci[j]); cols.push_back(c); cmin_w = std::min(cmin_w, c); cmax_w = std::max(cmax_w, c); }
-                    }
-                    // best 16-byte-aligned start: for every aligned start that holds an entry, the entries in [start, start + cap_cols); the
-                    // first start with the largest count wins.  (An entry c that is not the smallest of its aligned group counts fewer entries
-                    // than the group's smallest one -- which is itself inside [group start, c) -- so only group starts compete.)
-                    long long best = 0; int bs = 0;
-                    const long long g0 = cols.empty() ? 0 : cmin_w / A, ngrp = cols.empty() ? 0 : cmax_w / A - g0 + 1;
-                    if (!cols.empty() && ngrp <= 4 * (long long)cols.size() + 1024 && !force_sort) {
-                        // dense enough: a histogram over the aligned groups and a sliding sum -- O(entries + groups) instead of a sort
-                        hist.assign((size_t)ngrp + 1, 0);
-                        for (int c : cols) hist[(size_t)(c / A - g0)]++;
-                        const long long wg = cap_cols / A;                                  // groups per span
-                        long long run = 0;
-                        for (long long g = 0; g < std::min(wg, ngrp); ++g) run += hist[(size_t)g];
-                        for (long long g = 0; g < ngrp; ++g) {
-                            if (hist[(size_t)g] > 0 && run > best) { best = run; bs = (int)((g0 + g) * A); }
-                            run -= hist[(size_t)g];
-                            if (g + wg < ngrp) run += hist[(size_t)(g + wg)];
-                        }
-                    } else {
-                    std::sort(cols.begin(), cols.end());
-                    size_t hi_i = 0;
-                    for (size_t lo_i = 0; lo_i < cols.size(); ++lo_i) {
-                        if (lo_i && cols[lo_i] == cols[lo_i - 1]) continue;
-                        const long long st = (cols[lo_i] / A) * A;
-                        if (hi_i < lo_i) hi_i = lo_i;
-                        while (hi_i < cols.size() && cols[hi_i] < st + cap_cols) ++hi_i;
-                        // entries between the aligned start and cols[lo_i] belong to the span too, but they are < A away: ignore them
-                        const long long cnt = (long long)(hi_i - lo_i);
-                        if (cnt > best) { best = cnt; bs = (int)st; }
-                    }
-                    }
-                    hmin[w] = bs; hin[w] = best;
-                    hlen[w] = (int)std::min<long long>(cap_cols, xl - bs);
-                }
-            });
-            if (pass == 0) {
-                long long in_s = 0, all_s = 0;
-                for (int w : wlist) { in_s += hin[(size_t)w]; all_s += wnnz[(size_t)w]; }
-                if (100 * in_s < 55 * all_s) { std::fill(hin.begin(), hin.end(), 0); break; }     // cover stays 0: no hybrid windows
-            }
-            }
-            long long in = 0;
-            for (int w = 0; w < nW; ++w) in += hin[w];
-            const double cover = all > 0 ? (double)in / (double)all : 0.0;
-            if (p.opt.x_window_hybrid > 0 || cover >= 0.6) {
-                p.win_hybrid = true;
-                fit = 0; maxlen = 0;
-                for (int w = 0; w < nW; ++w) {
-                    // a window whose best span holds under a quarter of its gathers is not worth its copy: global gathers only
-                    if (hin[w] * 4 < wnnz[w] || hlen[w] <= 0) { cmin[w] = 0; wlen[w] = 0; continue; }
-                    cmin[w] = hmin[w]; wlen[w] = hlen[w]; fit += hin[w]; maxlen = std::max(maxlen, wlen[w]);
-                }
-                window_frac = all > 0 ? (double)fit / (double)all : 0.0;
-            }
-        }
-        bool worth = window_frac >= 0.5 && (double)all >= 0.5 * (double)nnz;
-        if (worth && !force && !order_only) {
-            // staging pays only when a row's gathers are scattered over the window: if neighbouring nonzeros of a row share
-            // 128-byte lines of x anyway (FEM / stencil rows: runs of adjacent columns), the L1 already serves them and the
-            // copy + window workgroups are pure overhead (HV15R x0.03: 18.2 -> 24.5 us, nlpkkt160 x0.01: 5.7 -> 8.5 us with
-            // windows; line-scatter 0.08-0.37 on the FEM-like stand-ins, 0.89-0.97 on the cop20k_A band)
-            std::vector<int> sample;
-            const int step = std::max(1, nmed / 2048);
-            for (int i = 0; i < nmed; i += step) sample.push_back(ridM_in[i]);
-            long long lines = 0, entries = 0;
-            if (dev) { if (int rc = devpack_line_scatter(p, *dev, sample, &lines, &entries)) return rc; }
-            else {
-                const int shift = geo.vbytes == 8 ? 4 : 6;
-                for (int r : sample) {
-                    const int b = rp[r], e = std::min(rp[r + 1], b + 512);
-                    int prev = remap(ci[b]) >> shift; lines += 1;
-                    for (int j = b + 1; j < e; ++j) { const int l = remap(ci[j]) >> shift; lines += l != prev; prev = l; }
-                    entries += e - b;
-                }
-            }
-            worth = entries > 0 && (double)lines >= 0.6 * (double)entries;
-            // r6: ... and only when a row's columns spread over more x than the L1 holds anyway.  The CORE span of a row -- 10th to 90th percentile of its columns, so that
-            // a few outliers do not count -- times the value size, median over the sampled rows: under 16 KB the 16 rows of a block gather from a few KB each and hit the
-            // L1, and the window's copy -> barrier -> blocks chain only costs (rows of 12 within +-500 columns + 10 % anywhere: 120 k rows f64 7.5 us with hybrid windows
-            // against 5.3-5.7 without, f16 6.0 / 4.2; 1 M rows f64 61.5 / 44.2; 500 k rows of 14 within +-3000 f16 25.2 / 19.6 -- while +-8000 f64 (102 KB) 181 -> 151 us,
-            // 200 k rows of 30 within +-2000 f64 (26 KB) 25.9 -> 22.7 and cop20k_A (51 KB) keep them: tools/hybrid_probe.py, gpurun_out/r6/call19.txt, call20.txt)
-            if (worth && p.opt.x_window_hybrid <= 0) {      // (a caller who forces the hybrid windows keeps them)
-                std::vector<int> fetched;
-                if (dev) {
-                    std::vector<long long> idx;
-                    for (int r : sample) for (int j = rp[r], e = std::min(rp[r + 1], rp[r] + 512); j < e; ++j) idx.push_back(j);
-                    if (int rc = devpack_gather_columns(p, *dev, &idx, 0, 0, 0, fetched)) return rc;
-                }
-                std::vector<long long> spans;
-                std::vector<int> cols;
-                size_t fpos = 0;
-                for (int r : sample) {
-                    const int b = rp[r], e = std::min(rp[r + 1], b + 512), len = e - b;
-                    cols.resize((size_t)len);
-                    if (dev) { for (int j = 0; j < len; ++j) cols[(size_t)j] = fetched[fpos + (size_t)j]; fpos += (size_t)len; }
-                    else for (int j = 0; j < len; ++j) cols[(size_t)j] = remap(ci[b + j]);
-                    if (len < 4) continue;
-                    std::sort(cols.begin(), cols.end());
-                    spans.push_back((long long)cols[(size_t)(len - 1 - len / 10)] - cols[(size_t)(len / 10)] + 1);
-                }
-                // ... provided the global length sort leaves neighbouring rows in one block (rows of one length: the block's 16 rows then share those few KB).  Rows of many
-                // lengths end up in blocks of rows from all over the matrix -- 16 such regions per chunk -- and keep their windows whatever their own span: cop20k_A in f16
-                // (12.8 KB per row) 6.9 -> 6.5 us, x4 22.0 -> 17.3 with windows.  The measure of the rule below: sampled blocks of the sorted order whose rows lie far apart.
-                int far = 0, cnt = 0;
-                {
-                    const int nblk = nmed / kMedRows, bstep = std::max(1, nblk / 512);
-                    for (int b = 0; b < nblk; b += bstep) {
-                        int lo = 2147483647, hi = -1;
-                        for (int i = b * kMedRows; i < (b + 1) * kMedRows; ++i) { lo = std::min(lo, ridM[i]); hi = std::max(hi, ridM[i]); }
-                        far += hi - lo > 16 * kMedRows; ++cnt;
-                    }
-                }
-                if (!spans.empty() && 2 * far < cnt) {
-                    std::nth_element(spans.begin(), spans.begin() + (long long)(spans.size() / 2), spans.end());
-                    if (spans[spans.size() / 2] * geo.vbytes < 16 * 1024) worth = false;
-                }
-            }
-            // ... or when it is the GLOBAL LENGTH SORT that scatters: rows of many different lengths whose columns are local (the strict windows fit, so they are) end up in
-            // blocks of 16 rows from all over the matrix -- 16 regions of x per chunk whatever the rows' own runs.  Windows sort inside R rows only and stage those rows' x
-            // (late r5, tools/scratch/window_order_probe.py / window_size_probe.py: 1 M local rows of 5..255 f64 0.571 -> 0.792 of the roofline, f16 0.623 -> 0.892; 4 M rows of
-            // 10..60 0.628 -> 0.722 / 0.546 -> 0.780; pays from ~8 M nonzeros on, so: >= 16 M).  Rows of one length (HV15R, Queen_4147) keep their row order in the sort and are
-            // not touched: measured as the span of row ids inside sampled blocks of the sorted order
-            if (!worth && nnz >= (16 << 20) && nmed >= 16 * 64) {
-                int far = 0, cnt = 0;
-                const int nblk = nmed / kMedRows, bstep = std::max(1, nblk / 512);
-                for (int b = 0; b < nblk; b += bstep) {
-                    int lo = 2147483647, hi = -1;
-                    for (int i = b * kMedRows; i < (b + 1) * kMedRows; ++i) { lo = std::min(lo, ridM[i]); hi = std::max(hi, ridM[i]); }
-                    // (not neighbours: more than 16 rows apart on average -- every row of the block then reads lines of its own; f16, whose 2-byte gathers use a 64th of every
-                    // line they miss: more than 4 apart -- 6 M tetra-like local rows of ~N(15,4) nonzeros, neighbours ~10 apart: f16 0.404 -> 0.514 with windows, f64 0.625 -> 0.653)
-                    far += hi - lo > (f16 ? 4 : 16) * kMedRows; ++cnt;
-                }
-                worth = cnt > 0 && 2 * far >= cnt;
-            }
-        }
-        if (!(((force || worth) && fit > 0) || order_only)) p.win_hybrid = false;
-        if (((force || worth) && fit > 0) || order_only) {
-            p.windowed = true; p.row_window = R;
-            p.lds_bytes = ((maxlen * geo.vbytes + 255) / 256) * 256;
-            p.win_cmin.swap(cmin); p.win_len.swap(wlen);
-            std::vector<int> slot_of_row((size_t)m, -1);
-            for (int i = 0; i < nmed; ++i) slot_of_row[ridM[i]] = nlong + i;       // reference slot of each (MFMA) medium row: p.med_slot0 + i
-            p.med_dst.resize(nmed);
-            for (int i = 0; i < nmed; ++i) p.med_dst[i] = natural ? rowdst(ridW[i]) : slot_of_row[ridW[i]];
-            ridM.swap(ridW); lenM.swap(lenW);                                      // the packers below follow the windowed order
         }
     }
+}
 
-    lap("window decision");
-    // ---- the longest medium rows as wave-sized pieces (opt.piece_min_len).  A 16-row block of rows with L nonzeros is a serial
-    // chain of ceil(L / K) MFMA steps in ONE wave, each batch of steps one memory latency; on a small matrix with a power-law
-    // tail the kernel then lasts as long as its longest block (webbase-1M stand-in, f16: rows of 255 = 16 steps = 8 batches ~ 8 us
-    // of a 14.6 us kernel).  Such rows are stored like the reference's long rows instead -- CSR order, one wave per piece, all 64
-    // lanes on one row -- while their slots in order_rid stay the medium rows' (they are the FIRST medium slots, right behind the
-    // long rows, so "index in the combined piece list == slot" holds as it does for the long rows).  Classifier counters unchanged.
-    int nsp = 0;
-    if (nmf > 0 && !meta_only && p.opt.piece_min_len >= 0 && !p.windowed) {   // window rows keep their LDS gathers (cop20k_A: 11.1 -> 14.7 us when split)
+// the automatic rule of decide_windows, asked once the windows cover half of the matrix: *pay = staging their x in LDS is worth its copy
+template <class T> static int windows_pay(const Build<T> &bld, bool *pay)
+{
+    const Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp;
+    const int nnz = bld.nnz, mfma_rows = bld.mfma_rows;
+    const bool f16 = bld.f16;
+    const raw_vector<int> &ridM = bld.ridM, &ridM_in = bld.ridM_in;
+    const CsrProbe probe = bld.probe();
+    bool worth = true;
+    // staging pays only when a row's gathers are scattered over the window: if neighbouring nonzeros of a row share
+    // 128-byte lines of x anyway (FEM / stencil rows: runs of adjacent columns), the L1 already serves them and the
+    // copy + window workgroups are pure overhead (HV15R x0.03: 18.2 -> 24.5 us, nlpkkt160 x0.01: 5.7 -> 8.5 us with
+    // windows; line-scatter 0.08-0.37 on the FEM-like stand-ins, 0.89-0.97 on the cop20k_A band)
+    std::vector<int> sample;
+    const int step = std::max(1, mfma_rows / 2048);
+    for (int i = 0; i < mfma_rows; i += step) sample.push_back(ridM_in[i]);
+    long long lines = 0, entries = 0;
+    if (int rc = probe.line_scatter(sample, geo.vbytes == 8 ? 4 : 6, 512, &lines, &entries)) return rc;
+    worth = entries > 0 && (double)lines >= 0.6 * (double)entries;
+    // r6: ... and only when a row's columns spread over more x than the L1 holds anyway.  The CORE span of a row -- 10th to 90th percentile of its columns, so that
+    // a few outliers do not count -- times the value size, median over the sampled rows: under 16 KB the 16 rows of a block gather from a few KB each and hit the
+    // L1, and the window's copy -> barrier -> blocks chain only costs (rows of 12 within +-500 columns + 10 % anywhere: 120 k rows f64 7.5 us with hybrid windows
+    // against 5.3-5.7 without, f16 6.0 / 4.2; 1 M rows f64 61.5 / 44.2; 500 k rows of 14 within +-3000 f16 25.2 / 19.6 -- while +-8000 f64 (102 KB) 181 -> 151 us,
+    // 200 k rows of 30 within +-2000 f64 (26 KB) 25.9 -> 22.7 and cop20k_A (51 KB) keep them: tools/hybrid_probe.py, gpurun_out/r6/call19.txt, call20.txt)
+    if (worth && p.opt.x_window_hybrid <= 0) {      // (a caller who forces the hybrid windows keeps them)
+        std::vector<int> fetched;      // the first 512 column ids of every sampled row
+        if (int rc = probe.columns_of_rows(sample, 512, fetched)) return rc;
+        std::vector<long long> spans;
+        std::vector<int> cols;
+        size_t fpos = 0;
+        for (int r : sample) {
+            const int b = rp[r], e = std::min(rp[r + 1], b + 512), len = e - b;
+            cols.resize((size_t)len);
+            for (int j = 0; j < len; ++j) cols[(size_t)j] = fetched[fpos + (size_t)j];
+            fpos += (size_t)len;
+            if (len < 4) continue;
+            std::sort(cols.begin(), cols.end());
+            spans.push_back((long long)cols[(size_t)(len - 1 - len / 10)] - cols[(size_t)(len / 10)] + 1);
+        }
+        // ... provided the global length sort leaves neighbouring rows in one block (rows of one length: the block's 16 rows then share those few KB).  Rows of many
+        // lengths end up in blocks of rows from all over the matrix -- 16 such regions per chunk -- and keep their windows whatever their own span: cop20k_A in f16
+        // (12.8 KB per row) 6.9 -> 6.5 us, x4 22.0 -> 17.3 with windows.  The measure of the rule below: sampled blocks of the sorted order whose rows lie far apart.
+        int far = 0, cnt = 0;
+        {
+            const int nblk = mfma_rows / kMedRows, bstep = std::max(1, nblk / 512);
+            for (int b = 0; b < nblk; b += bstep) {
+                int lo = 2147483647, hi = -1;
+                for (int i = b * kMedRows; i < (b + 1) * kMedRows; ++i) { lo = std::min(lo, ridM[i]); hi = std::max(hi, ridM[i]); }
+                far += hi - lo > 16 * kMedRows; ++cnt;
+            }
+        }
+        if (!spans.empty() && 2 * far < cnt) {
+            std::nth_element(spans.begin(), spans.begin() + (long long)(spans.size() / 2), spans.end());
+            if (spans[spans.size() / 2] * geo.vbytes < 16 * 1024) worth = false;
+        }
+    }
+    // ... or when it is the GLOBAL LENGTH SORT that scatters: rows of many different lengths whose columns are local (the strict windows fit, so they are) end up in
+    // blocks of 16 rows from all over the matrix -- 16 regions of x per chunk whatever the rows' own runs.  Windows sort inside R rows only and stage those rows' x
+    // (late r5, tools/scratch/window_order_probe.py / window_size_probe.py: 1 M local rows of 5..255 f64 0.571 -> 0.792 of the roofline, f16 0.623 -> 0.892; 4 M rows of
+    // 10..60 0.628 -> 0.722 / 0.546 -> 0.780; pays from ~8 M nonzeros on, so: >= 16 M).  Rows of one length (HV15R, Queen_4147) keep their row order in the sort and are
+    // not touched: measured as the span of row ids inside sampled blocks of the sorted order
+    if (!worth && nnz >= (16 << 20) && mfma_rows >= 16 * 64) {
+        int far = 0, cnt = 0;
+        const int nblk = mfma_rows / kMedRows, bstep = std::max(1, nblk / 512);
+        for (int b = 0; b < nblk; b += bstep) {
+            int lo = 2147483647, hi = -1;
+            for (int i = b * kMedRows; i < (b + 1) * kMedRows; ++i) { lo = std::min(lo, ridM[i]); hi = std::max(hi, ridM[i]); }
+            // (not neighbours: more than 16 rows apart on average -- every row of the block then reads lines of its own; f16, whose 2-byte gathers use a 64th of every
+            // line they miss: more than 4 apart -- 6 M tetra-like local rows of ~N(15,4) nonzeros, neighbours ~10 apart: f16 0.404 -> 0.514 with windows, f64 0.625 -> 0.653)
+            far += hi - lo > (f16 ? 4 : 16) * kMedRows; ++cnt;
+        }
+        worth = cnt > 0 && 2 * far >= cnt;
+    }
+    *pay = worth;
+    return DASP_OK;
+}
+
+// ---- optional windowed order for the medium rows (LDS-staged x).  The reference sorts all
+// medium rows globally by length, which scatters the 16 rows of a block over the matrix; here rows are sorted inside
+// windows of `row_window` consecutive medium rows only, one window per workgroup, so a workgroup's rows share a narrow
+// span of x that is staged once in LDS.  Output slots stay the reference's (order_rid untouched): y goes through med_dst.
+template <class T> static int decide_windows(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int m = bld.m, nnz = bld.nnz, mfma_rows = bld.mfma_rows, row_long = bld.row_long;
+    p.windowed = false; p.win_hybrid = false; p.win_rel16 = false; p.row_window = 0; p.lds_bytes = 0;
+    p.med_dst.clear(); p.win_cmin.clear(); p.win_len.clear();
+    bld.window_frac = 0.0;
+    if (!((p.opt.x_window >= 0 || p.opt.x_window == -2) && mfma_rows > 0 && !bld.meta_only)) { bld.lap("window decision"); return DASP_OK; }
+    Windows w;
+    w.R = default_row_window(bld);
+    w.nW = ceil_div(mfma_rows, w.R);
+    // default cap: 80 KiB = two workgroups per CU out of gfx950's 160 KiB of LDS
+    w.order_only = p.opt.x_window == -2;
+    w.cap_bytes = w.order_only ? 0 : (p.opt.x_window > 0 ? std::min(p.opt.x_window, kWinLdsMax) : 80 * 1024);
+    w.A = 16 / geo.vbytes;
+    order_in_windows(bld, w);
+    if (int rc = scan_window_spans(bld, w)) return rc;
+    fit_windows(bld, w);
+    // auto: when the spans are too wide for two workgroups per CU (80 KiB each), one workgroup per CU with all of the LDS
+    // still beats global gathers on band-scattered rows (+-30 k columns, f16: 98.8 -> 65.9 us; +-8 k, f64: 166.8 -> 115.8 us)
+    if (p.opt.x_window == 0 && bld.window_frac < 0.5) { w.cap_bytes = kWinLdsMax; fit_windows(bld, w); }
+    const bool force = p.opt.x_window > 0;
+    hybrid_windows(bld, w);
+    bool worth = bld.window_frac >= 0.5 && (double)w.all >= 0.5 * (double)nnz;
+    if (worth && !force && !w.order_only) { if (int rc = windows_pay(bld, &worth)) return rc; }
+    const int R = w.R;
+    if (!(((force || worth) && w.fit > 0) || w.order_only)) p.win_hybrid = false;
+    if (((force || worth) && w.fit > 0) || w.order_only) {
+        p.windowed = true; p.row_window = R;
+        p.lds_bytes = ((w.maxlen * geo.vbytes + 255) / 256) * 256;
+        p.win_cmin.swap(w.cmin); p.win_len.swap(w.wlen);
+        std::vector<int> slot_of_row((size_t)m, -1);
+        for (int i = 0; i < mfma_rows; ++i) slot_of_row[bld.ridM[i]] = row_long + i;       // reference slot of each (MFMA) medium row: p.med_slot0 + i
+        p.med_dst.resize(mfma_rows);
+        for (int i = 0; i < mfma_rows; ++i) p.med_dst[i] = bld.natural ? bld.rowdst(w.ridW[i]) : slot_of_row[w.ridW[i]];
+        bld.ridM.swap(w.ridW); bld.lenM.swap(w.lenW);                                      // the packers below follow the windowed order
+    }
+
+    bld.lap("window decision");
+    return DASP_OK;
+}
+
+// ---- the longest medium rows as wave-sized pieces (opt.piece_min_len).  A 16-row block of rows with L nonzeros is a serial
+// chain of ceil(L / K) MFMA steps in ONE wave, each batch of steps one memory latency; on a small matrix with a power-law
+// tail the kernel then lasts as long as its longest block (webbase-1M stand-in, f16: rows of 255 = 16 steps = 8 batches ~ 8 us
+// of a 14.6 us kernel).  Such rows are stored like the reference's long rows instead -- CSR order, one wave per piece, all 64
+// lanes on one row -- while their slots in order_rid stay the medium rows' (they are the FIRST medium slots, right behind the
+// long rows, so "index in the combined piece list == slot" holds as it does for the long rows).  Classifier counters unchanged.
+template <class T> static int medium_rows_as_pieces(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp;
+    const int nnz = bld.nnz;
+    const bool f16 = bld.f16, meta_only = bld.meta_only;
+    std::vector<int> &ridL = bld.ridL;
+    raw_vector<int> &ridM = bld.ridM, &lenM = bld.lenM, &ridM_in = bld.ridM_in;
+    int &mfma_rows = bld.mfma_rows, &nsp = bld.nsp;
+    nsp = 0;
+    if (mfma_rows > 0 && !meta_only && p.opt.piece_min_len >= 0 && !p.windowed) {   // window rows keep their LDS gathers (cop20k_A: 11.1 -> 14.7 us when split)
         int Tmin = p.opt.piece_min_len > 0 ? std::max(5, p.opt.piece_min_len) : 0;
         if (Tmin == 0) {
             // auto: only when the matrix is latency-bound (a couple of batches of the longest block already take as long as
@@ -941,8 +1248,8 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
             // never cut inside a run of equal lengths (the row-order list is filtered by length below)
             const bool forced = p.opt.piece_min_len > 0;
             int cnt = 0; long long k = 0;
-            while (cnt < nmf && lenM[cnt] >= Tmin && (forced || (k + lenM[cnt]) * 100 <= 15ll * nnz)) { k += lenM[cnt]; ++cnt; }
-            while (cnt > 0 && cnt < nmf && lenM[cnt] == lenM[cnt - 1]) --cnt;
+            while (cnt < mfma_rows && lenM[cnt] >= Tmin && (forced || (k + lenM[cnt]) * 100 <= 15ll * nnz)) { k += lenM[cnt]; ++cnt; }
+            while (cnt > 0 && cnt < mfma_rows && lenM[cnt] == lenM[cnt - 1]) --cnt;
             nsp = cnt;
         }
     }
@@ -953,14 +1260,28 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         raw_vector<int> keep; keep.reserve(ridM_in.size());
         for (int r : ridM_in) if (rp[r + 1] - rp[r] < Tcut) keep.push_back(r);
         ridM_in.swap(keep);
-        nmf -= nsp; nmed = nmf; nlong += nsp;         // from here on nlong counts the rows STORED as pieces
+        mfma_rows -= nsp;
     }
-    p.med_slot0 = nlong;
-    p.n_mfma_rows = nmf;
+    bld.rows_as_pieces = bld.row_long + nsp;
+    p.med_slot0 = bld.rows_as_pieces;
+    p.n_mfma_rows = mfma_rows;
+    return DASP_OK;
+}
+
+// ---- long rows: compact, padded to kLongAlign; one wave per piece
+template <class T> static int pack_long(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp, *ci = bld.ci;
+    const T *val = bld.val;
+    const Remap remap = bld.remap;
+    const int nnz = bld.nnz, threads = bld.threads, rows_as_pieces = bld.rows_as_pieces;
+    const bool f16 = bld.f16, pack = bld.pack;
+    const std::vector<int> &ridL = bld.ridL;
+    std::vector<long long> &startL = bld.startL;
     long long nnz_pieces = 0;
     for (int r : ridL) nnz_pieces += rp[r + 1] - rp[r];
-    // ---- long rows: compact, padded to kLongAlign; one wave per piece
-    std::vector<long long> startL;
     int piece = p.opt.long_piece > 0 ? p.opt.long_piece : 1024;
     if (p.opt.long_piece <= 0) {
         // one piece per row, so that the second launch (long_reduce) disappears, when that leaves no wave with a long tail of its own: few
@@ -978,12 +1299,12 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     }
     piece = std::max(geo.chunk, ceil_div(piece, geo.chunk) * geo.chunk);
     {
-        std::vector<long long> start((size_t)nlong + 1, 0);
-        for (int i = 0; i < nlong; ++i) {
+        std::vector<long long> start((size_t)rows_as_pieces + 1, 0);
+        for (int i = 0; i < rows_as_pieces; ++i) {
             const int len = rp[ridL[i] + 1] - rp[ridL[i]];
             start[i + 1] = start[i] + (long long)ceil_div(len, kLongAlign) * kLongAlign;
         }
-        const long long total = start[nlong];
+        const long long total = start[rows_as_pieces];
         if (total >= (1LL << 31)) { set_error("long-row segment exceeds 2^31 elements"); return DASP_ERR_ARG; }
         p.cnt_long = (size_t)total;
         startL = start;
@@ -994,21 +1315,21 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         }
         p.piece_ptr.clear(); p.piece_dst.clear(); p.multi_ptr.assign(1, 0); p.multi_dst.clear();
         int n_partial = 0;
-        for (int i = 0; i < nlong; ++i) {
+        for (int i = 0; i < rows_as_pieces; ++i) {
             const long long lp = start[i + 1] - start[i];
             const int np = (int)((lp + piece - 1) / piece);
             for (int q = 0; q < np; ++q) {
                 p.piece_ptr.push_back((int)(start[i] + (long long)q * piece));
-                p.piece_dst.push_back(np == 1 ? ydst(i) : ~(n_partial++));
+                p.piece_dst.push_back(np == 1 ? bld.ydst(i) : ~(n_partial++));
             }
-            if (np > 1) { p.multi_ptr.push_back(n_partial); p.multi_dst.push_back(ydst(i)); }
+            if (np > 1) { p.multi_ptr.push_back(n_partial); p.multi_dst.push_back(bld.ydst(i)); }
         }
         p.piece_ptr.push_back((int)total);
         T *lv = reinterpret_cast<T *>(p.long_val.data());
         // element-parallel (not row-parallel): a power-law matrix keeps most of its long nonzeros in a handful of rows
         if (pack) parallel_for(total, threads, 1 << 16, [&](long long b, long long e) {
             long long i = std::upper_bound(start.begin(), start.end(), b) - start.begin() - 1;   // row holding element b
-            for (; i < nlong && start[i] < e; ++i) {
+            for (; i < rows_as_pieces && start[i] < e; ++i) {
                 const int r = ridL[i], len = rp[r + 1] - rp[r];
                 const long long s0 = std::max(b, start[i]), s1 = std::min(e, start[i + 1]);
                 const long long real_end = std::min(s1, start[i] + len);
@@ -1051,13 +1372,24 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         }
     }
 
-    lap("long rows");
-    // ---- medium rows: regular tiles kept while a 16 x K chunk is >= threshold full
-    // (the reference's rule, dasp_f64.h:1044-1091, on this geometry's tile), rest = irregular tail
-    const int K = geo.med_k, CH = geo.chunk, VPL = geo.chunk / 64;      // values of one chunk per lane: 1 (f64) / 4 (f16)
-    const int nb = ceil_div(nmed, kMedRows);
+    bld.lap("long rows");
+    return DASP_OK;
+}
+
+// ---- medium rows: regular tiles kept while a 16 x K chunk is >= threshold full
+// (the reference's rule, dasp_f64.h:1044-1091, on this geometry's tile), rest = irregular tail
+template <class T> static int split_medium_chunks(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int nnz = bld.nnz, threads = bld.threads, mfma_rows = bld.mfma_rows;
+    const bool f16 = bld.f16, meta_only = bld.meta_only, pack = bld.pack;
+    const double threshold = p.opt.threshold;
+    const raw_vector<int> &ridM = bld.ridM, &lenM = bld.lenM;
+    const int K = geo.med_k, CH = geo.chunk;
+    const int nb = bld.nb = ceil_div(mfma_rows, kMedRows);
     std::vector<int> nchunks((size_t)nb + 1, 0);
-    p.irr_ptr.assign((size_t)nmed + 1, 0);
+    p.irr_ptr.assign((size_t)mfma_rows + 1, 0);
     // 16-bit column ids: a chunk's ids are stored as u16 offsets from the chunk's smallest column (one int32 base per
     // chunk), 10 instead of 12 bytes per f64 nonzero (4 instead of 6 for f16).  A chunk whose columns span more than
     // 65534 cannot be stored that way; in cid16 mode the regular part of its block ends there and the rest of those rows
@@ -1070,32 +1402,17 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     std::vector<unsigned long long> narrow_mask(try8 ? (size_t)nb : 0, 0ull);
     parallel_for(nb, threads, 256, [&](long long b0, long long b1) {
         for (long long b = b0; b < b1; ++b) {
-            const int r0 = (int)b * kMedRows, r1 = std::min(nmed, r0 + kMedRows);
+            const int r0 = (int)b * kMedRows, r1 = std::min(mfma_rows, r0 + kMedRows);
             int k = 0;
             for (;; ++k) {
                 int fill = 0;
                 for (int r = r0; r < r1; ++r) fill += std::min(K, std::max(0, lenM[r] - K * k));
                 if (!(fill >= threshold * CH) || fill == 0) break;
             }
-            nchunks[b] = k;
-            int k16 = k;
-            unsigned long long mask = 0;
-            if (try16 && !dev) {
-                for (int c = 0; c < k; ++c) {
-                    int lo = 2147483647, hi = -1;
-                    for (int r = r0; r < r1; ++r) {
-                        const int a0 = rp[ridM[r]], i0 = c * K, i1 = std::min(lenM[r], i0 + K);
-                        for (int i = i0; i < i1; ++i) { const int col = remap(ci[a0 + i]); lo = std::min(lo, col); hi = std::max(hi, col); }
-                    }
-                    if (hi >= 0 && (long long)hi - lo > 65534) { k16 = c; break; }
-                    if (c < 64 && hi >= 0 && hi - lo <= 254) mask |= 1ull << c;
-                }
-            }
-            nchunks16[b] = k16;
-            if (try8 && !dev) narrow_mask[(size_t)b] = mask;
+            nchunks[b] = k; nchunks16[b] = k;      // (16-bit ids: the chunk spans below may end the block's regular part earlier)
         }
     });
-    if (try16 && dev) { if (int rc = devpack_chunk_spans(p, *dev, ridM, lenM, nchunks, nchunks16.data(), try8 ? narrow_mask.data() : nullptr)) return rc; }
+    if (try16) { if (int rc = bld.probe().chunk_spans(ridM, lenM, nchunks, K, nchunks16.data(), try8 ? narrow_mask.data() : nullptr)) return rc; }
     {
         long long e32 = 0, e16 = 0;
         for (int b = 0; b < nb; ++b) { e32 += nchunks[b]; e16 += nchunks16[b]; }
@@ -1117,7 +1434,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     }
     parallel_for(nb, threads, 1 << 12, [&](long long b0, long long b1) {
         for (long long b = b0; b < b1; ++b) {
-            const int r0 = (int)b * kMedRows, r1 = std::min(nmed, r0 + kMedRows);
+            const int r0 = (int)b * kMedRows, r1 = std::min(mfma_rows, r0 + kMedRows);
             for (int r = r0; r < r1; ++r) p.irr_ptr[(size_t)r] = std::max(0, lenM[(size_t)r] - K * nchunks[(size_t)b]);
         }
     });
@@ -1143,7 +1460,7 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         // build with its longer id decode loses (HV15R x0.01, 30 MB: 8.1 -> 9.1 us when the lower 16-bit bound of r6 brought them along: tests/test_zz_auto_rules.py)
         if (p.opt.cid8 == 0 && p.opt.cid16 == 0 && (long long)nnz * (geo.vbytes + 4) <= (64ll << 20)) std::fill(n8of.begin(), n8of.end(), 0);      // (a caller who forces the 16-bit ids on a small matrix keeps the r5 rule)
     }
-    lap("chunk split (+cid16 spans)");
+    bld.lap("chunk split (+cid16 spans)");
     p.med_ptr.assign((size_t)nb + 1, 0);
     {
         long long run = 0;
@@ -1151,12 +1468,12 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         if (run >= (1LL << 31) / 1) { set_error("too many medium chunks"); return DASP_ERR_ARG; }
         p.med_ptr[nb] = (int)run;
         // exclusive scan of the tail lengths: per-range sums, their prefix, then every range scans itself
-        const int sparts = (int)std::max<long long>(1, std::min<long long>(threads, ((long long)nmed + (1 << 16) - 1) >> 16));
+        const int sparts = (int)std::max<long long>(1, std::min<long long>(threads, ((long long)mfma_rows + (1 << 16) - 1) >> 16));
         std::vector<long long> psum((size_t)sparts + 1, 0);
         parallel_for(sparts, sparts, 1, [&](long long p0, long long p1) {
             for (long long q = p0; q < p1; ++q) {
                 long long a = 0;
-                for (long long r = (long long)nmed * q / sparts, e = (long long)nmed * (q + 1) / sparts; r < e; ++r) a += p.irr_ptr[(size_t)r];
+                for (long long r = (long long)mfma_rows * q / sparts, e = (long long)mfma_rows * (q + 1) / sparts; r < e; ++r) a += p.irr_ptr[(size_t)r];
                 psum[(size_t)q + 1] = a;
             }
         });
@@ -1164,15 +1481,15 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         parallel_for(sparts, sparts, 1, [&](long long p0, long long p1) {
             for (long long q = p0; q < p1; ++q) {
                 long long t = psum[(size_t)q];
-                for (long long r = (long long)nmed * q / sparts, e = (long long)nmed * (q + 1) / sparts; r < e; ++r) { const int v = p.irr_ptr[(size_t)r]; p.irr_ptr[(size_t)r] = (int)t; t += v; }
+                for (long long r = (long long)mfma_rows * q / sparts, e = (long long)mfma_rows * (q + 1) / sparts; r < e; ++r) { const int v = p.irr_ptr[(size_t)r]; p.irr_ptr[(size_t)r] = (int)t; t += v; }
             }
         });
         long long t = psum[(size_t)sparts];
-        p.irr_ptr[nmed] = (int)t;
+        p.irr_ptr[mfma_rows] = (int)t;
     }
-    const long long n_reg = (long long)p.med_ptr[nb] * CH;
-    const int nnz_irreg = p.irr_ptr[nmed];
-    p.cnt_reg = (size_t)n_reg; p.cnt_irr = (size_t)nnz_irreg;
+    bld.n_reg = (long long)p.med_ptr[nb] * CH;
+    bld.nnz_irreg = p.irr_ptr[mfma_rows];
+    p.cnt_reg = (size_t)bld.n_reg; p.cnt_irr = (size_t)bld.nnz_irreg;
     p.med_base.assign(p.cid16 && pack ? (size_t)p.med_ptr[nb] : 0, 0);
     p.med_c8ptr.clear(); p.med_korig.clear(); p.med_cid8.clear(); p.cnt_reg8 = 0;
     if (p.cid16) {
@@ -1181,7 +1498,23 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
         p.cnt_reg8 = (size_t)p.med_c8ptr[nb] * CH;
         p.med_korig.assign((size_t)p.med_ptr[nb], 0);
     }
-    if (pack) {
+    return DASP_OK;
+}
+
+// ---- medium rows: the regular chunks and the irregular tails written (host packing only)
+template <class T> static int pack_medium(Build<T> &bld)
+{
+    if (!bld.pack) { bld.lap("pack medium"); return DASP_OK; }
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp, *ci = bld.ci;
+    const T *val = bld.val;
+    const Remap remap = bld.remap;
+    const int threads = bld.threads, mfma_rows = bld.mfma_rows, nb = bld.nb, nnz_irreg = bld.nnz_irreg;
+    const long long n_reg = bld.n_reg;
+    const bool f16 = bld.f16;
+    const raw_vector<int> &ridM = bld.ridM, &lenM = bld.lenM;
+    const int K = geo.med_k, CH = geo.chunk, VPL = geo.chunk / 64;      // values of one chunk per lane: 1 (f64) / 4 (f16)
     p.med_val.resize((size_t)n_reg * sizeof(T));               // not zero-filled: each block pads its own region first
     p.med_cid.resize(p.cid16 ? 0 : (size_t)n_reg);
     p.med_cid16.resize(p.cid16 ? (size_t)n_reg - p.cnt_reg8 : 0);
@@ -1189,169 +1522,185 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     p.irr_val.resize((size_t)nnz_irreg * sizeof(T));           // fully covered by the rows' tails
     p.irr_cid.resize((size_t)nnz_irreg);
     if (p.value_map) { p.med_map.assign((size_t)n_reg, 0u); p.irr_map.assign((size_t)nnz_irreg, 0u); }      // pads stay 0
-    }
-    if (pack) {
-        T *mv = reinterpret_cast<T *>(p.med_val.data());
-        T *iv = reinterpret_cast<T *>(p.irr_val.data());
-        parallel_for(nb, threads, 64, [&](long long b0, long long b1) {
-            std::vector<int> pos_of, lo_of;
-            for (long long b = b0; b < b1; ++b) {
-                const int nc = p.med_ptr[b + 1] - p.med_ptr[b];
-                const size_t base = (size_t)p.med_ptr[b] * CH;
-                const int r0 = (int)b * kMedRows, r1 = std::min(nmed, r0 + kMedRows);
-                // tail steps of the block = those of its first (longest) row; with them the kernel decides one shot / pipeline, hence the layout
-                const int nt_b = (p.irr_ptr[r0 + 1] - p.irr_ptr[r0] + K - 1) / K;
-                const int npair = med_npair(nc, nt_b, geo.vbytes, p.pair_mode);
-                const bool oneshot = med_oneshot64(nc, nt_b);          // (f64: the layout of the block's one-byte ids)
-                // cid16 mode: position q of the block holds the block's chunk korig[q]: n8 narrow chunks (columns span <= 254: one-byte ids) of
-                // the paired region first, everything else behind them in its original order
-                const int n8 = p.cid16 ? p.med_c8ptr[b + 1] - p.med_c8ptr[b] : 0;
-                const size_t e8 = p.cid16 ? (size_t)p.med_c8ptr[b] * CH : 0;                               // the block's narrow ids in med_cid8
-                const size_t e16 = p.cid16 ? ((size_t)p.med_ptr[b] - (size_t)p.med_c8ptr[b]) * CH : 0;      // its wide ids in med_cid16
-                pos_of.assign((size_t)nc + 1, 0); lo_of.assign((size_t)nc + 1, 0);
-                if (p.cid16) {
-                    int a8 = 0, a16 = 0;
-                    for (int c = 0; c < nc; ++c) {
-                        int lo = 2147483647, hi = -1;
-                        for (int r = r0; r < r1; ++r) {
-                            const int a0 = rp[ridM[r]], i0 = c * K, i1 = std::min(lenM[r], i0 + K);
-                            for (int i = i0; i < i1; ++i) { const int col = remap(ci[a0 + i]); lo = std::min(lo, col); hi = std::max(hi, col); }
-                        }
-                        const bool narrow = c < npair && c < 64 && a8 < n8 && hi >= 0 && hi - lo <= 254;
-                        lo_of[c] = lo == 2147483647 ? 0 : lo;
-                        if (p.win_rel16) { const size_t w = (size_t)b / (size_t)(p.row_window / kMedRows); if (p.win_len[w] > 0) lo_of[c] = p.win_cmin[w]; }
-                        pos_of[c] = c >= npair ? c : narrow ? a8++ : n8 + a16++;
+    T *mv = reinterpret_cast<T *>(p.med_val.data());
+    T *iv = reinterpret_cast<T *>(p.irr_val.data());
+    parallel_for(nb, threads, 64, [&](long long b0, long long b1) {
+        std::vector<int> pos_of, lo_of;
+        for (long long b = b0; b < b1; ++b) {
+            const int nc = p.med_ptr[b + 1] - p.med_ptr[b];
+            const size_t base = (size_t)p.med_ptr[b] * CH;
+            const int r0 = (int)b * kMedRows, r1 = std::min(mfma_rows, r0 + kMedRows);
+            // tail steps of the block = those of its first (longest) row; with them the kernel decides one shot / pipeline, hence the layout
+            const int nt_b = (p.irr_ptr[r0 + 1] - p.irr_ptr[r0] + K - 1) / K;
+            const int npair = med_npair(nc, nt_b, geo.vbytes, p.pair_mode);
+            const bool oneshot = med_oneshot64(nc, nt_b);          // (f64: the layout of the block's one-byte ids)
+            // cid16 mode: position q of the block holds the block's chunk korig[q]: n8 narrow chunks (columns span <= 254: one-byte ids) of
+            // the paired region first, everything else behind them in its original order
+            const int n8 = p.cid16 ? p.med_c8ptr[b + 1] - p.med_c8ptr[b] : 0;
+            const size_t e8 = p.cid16 ? (size_t)p.med_c8ptr[b] * CH : 0;                               // the block's narrow ids in med_cid8
+            const size_t e16 = p.cid16 ? ((size_t)p.med_ptr[b] - (size_t)p.med_c8ptr[b]) * CH : 0;      // its wide ids in med_cid16
+            pos_of.assign((size_t)nc + 1, 0); lo_of.assign((size_t)nc + 1, 0);
+            if (p.cid16) {
+                int a8 = 0, a16 = 0;
+                for (int c = 0; c < nc; ++c) {
+                    int lo = 2147483647, hi = -1;
+                    for (int r = r0; r < r1; ++r) {
+                        const int a0 = rp[ridM[r]], i0 = c * K, i1 = std::min(lenM[r], i0 + K);
+                        for (int i = i0; i < i1; ++i) { const int col = remap(ci[a0 + i]); lo = std::min(lo, col); hi = std::max(hi, col); }
                     }
-                    for (int c = 0; c < nc; ++c) {
-                        p.med_base[(size_t)p.med_ptr[b] + pos_of[c]] = lo_of[c];
-                        p.med_korig[(size_t)p.med_ptr[b] + pos_of[c]] = c;
-                    }
-                } else for (int c = 0; c < nc; ++c) pos_of[c] = c;
-                {   // pad the block's region (value 0, id -1 / 0xFFFF / 0xFF); real entries overwrite below
-                    const size_t n = (size_t)nc * CH;
-                    std::fill(mv + base, mv + base + n, (T)0);
-                    if (p.cid16) {
-                        std::fill(p.med_cid8.begin() + e8, p.med_cid8.begin() + e8 + (size_t)n8 * CH, (uint8_t)0xFF);
-                        std::fill(p.med_cid16.begin() + e16, p.med_cid16.begin() + e16 + (size_t)(nc - n8) * CH, (uint16_t)0xFFFF);
-                    } else std::fill(p.med_cid.begin() + base, p.med_cid.begin() + base + n, -1);
+                    const bool narrow = c < npair && c < 64 && a8 < n8 && hi >= 0 && hi - lo <= 254;
+                    lo_of[c] = lo == 2147483647 ? 0 : lo;
+                    if (p.win_rel16) { const size_t w = (size_t)b / (size_t)(p.row_window / kMedRows); if (p.win_len[w] > 0) lo_of[c] = p.win_cmin[w]; }
+                    pos_of[c] = c >= npair ? c : narrow ? a8++ : n8 + a16++;
                 }
-                for (int r = r0; r < r1; ++r) {
-                    const int rr = r - r0, row = ridM[r], len = lenM[r], a0 = rp[row];
-                    const int nreg = std::min(len, nc * K);
-                    for (int i = 0; i < nreg; ++i) {
-                        const int c = i / K, kk = i % K, q = pos_of[c];
-                        // f64: lane = kk*16 + rr holds A[rr][kk]            (one value per lane)
-                        // f16: lane = (kk/4)*16 + rr holds A[rr][4*(kk/4)..+3] (four values per lane)
-                        // a pipelined block's leading chunks are stored in pairs, [pair][lane][2 chunks][VPL] (plan.hpp med_npair)
-                        const int lane = f16 ? (kk / 4) * kMedRows + rr : kk * kMedRows + rr, j = f16 ? kk % 4 : 0;
-                        const size_t at = base + med_elem_index(npair, q, lane, j, VPL, CH);
-                        mv[at] = val[a0 + i];
-                        if (p.value_map) p.med_map[at] = map_entry(p, a0 + i);
-                        const int col = remap(ci[a0 + i]);
-                        if (!p.cid16) p.med_cid[at] = col;
-                        else if (q < n8) p.med_cid8[e8 + med_cid8_index(q, lane, CH, oneshot)] = (uint8_t)(col - lo_of[c]);
-                        else p.med_cid16[e16 + med_elem_index(npair - n8, q - n8, lane, j, VPL, CH)] = (uint16_t)(col - lo_of[c]);
-                    }
-                    const int t0 = p.irr_ptr[r], tl = p.irr_ptr[r + 1] - t0;
-                    for (int j = 0; j < tl; ++j) {   // the LAST tl entries of the row (dasp_f64.h:1094-1106)
-                        iv[t0 + j] = val[a0 + len - tl + j];
-                        if (p.value_map) p.irr_map[(size_t)(t0 + j)] = map_entry(p, a0 + len - tl + j);
-                        p.irr_cid[t0 + j] = remap(ci[a0 + len - tl + j]);
-                    }
+                for (int c = 0; c < nc; ++c) {
+                    p.med_base[(size_t)p.med_ptr[b] + pos_of[c]] = lo_of[c];
+                    p.med_korig[(size_t)p.med_ptr[b] + pos_of[c]] = c;
+                }
+            } else for (int c = 0; c < nc; ++c) pos_of[c] = c;
+            {   // pad the block's region (value 0, id -1 / 0xFFFF / 0xFF); real entries overwrite below
+                const size_t n = (size_t)nc * CH;
+                std::fill(mv + base, mv + base + n, (T)0);
+                if (p.cid16) {
+                    std::fill(p.med_cid8.begin() + e8, p.med_cid8.begin() + e8 + (size_t)n8 * CH, (uint8_t)0xFF);
+                    std::fill(p.med_cid16.begin() + e16, p.med_cid16.begin() + e16 + (size_t)(nc - n8) * CH, (uint16_t)0xFFFF);
+                } else std::fill(p.med_cid.begin() + base, p.med_cid.begin() + base + n, -1);
+            }
+            for (int r = r0; r < r1; ++r) {
+                const int rr = r - r0, row = ridM[r], len = lenM[r], a0 = rp[row];
+                const int nreg = std::min(len, nc * K);
+                for (int i = 0; i < nreg; ++i) {
+                    const int c = i / K, kk = i % K, q = pos_of[c];
+                    // f64: lane = kk*16 + rr holds A[rr][kk]            (one value per lane)
+                    // f16: lane = (kk/4)*16 + rr holds A[rr][4*(kk/4)..+3] (four values per lane)
+                    // a pipelined block's leading chunks are stored in pairs, [pair][lane][2 chunks][VPL] (plan.hpp med_npair)
+                    const int lane = f16 ? (kk / 4) * kMedRows + rr : kk * kMedRows + rr, j = f16 ? kk % 4 : 0;
+                    const size_t at = base + med_elem_index(npair, q, lane, j, VPL, CH);
+                    mv[at] = val[a0 + i];
+                    if (p.value_map) p.med_map[at] = map_entry(p, a0 + i);
+                    const int col = remap(ci[a0 + i]);
+                    if (!p.cid16) p.med_cid[at] = col;
+                    else if (q < n8) p.med_cid8[e8 + med_cid8_index(q, lane, CH, oneshot)] = (uint8_t)(col - lo_of[c]);
+                    else p.med_cid16[e16 + med_elem_index(npair - n8, q - n8, lane, j, VPL, CH)] = (uint16_t)(col - lo_of[c]);
+                }
+                const int t0 = p.irr_ptr[r], tl = p.irr_ptr[r + 1] - t0;
+                for (int j = 0; j < tl; ++j) {   // the LAST tl entries of the row (dasp_f64.h:1094-1106)
+                    iv[t0 + j] = val[a0 + len - tl + j];
+                    if (p.value_map) p.irr_map[(size_t)(t0 + j)] = map_entry(p, a0 + len - tl + j);
+                    p.irr_cid[t0 + j] = remap(ci[a0 + len - tl + j]);
+                }
+            }
+        }
+    });
+
+    bld.lap("pack medium");
+    return DASP_OK;
+}
+
+// ---- short rows: one slab per length, tile-major [tile][k][short_rows] -- or, for the rows of 1..4 nonzeros, the wave-segmented layout
+// (opt.short_seg, plan.hpp short_elem_index): auto = f64 plans without x windows (the windowed kernels are held to 64 registers and
+// spill more with the DPP path compiled in: cop20k_A 11.1 -> 12.0 us; f16 gains nothing: DESIGN.md section 3)
+template <class T> static int pack_short(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const int *rp = bld.rp, *ci = bld.ci;
+    const T *val = bld.val;
+    const Remap remap = bld.remap;
+    const int threads = bld.threads, nnz_short = bld.nnz_short;
+    const bool f16 = bld.f16, meta_only = bld.meta_only, pack = bld.pack;
+    const std::vector<int> *const *glist = bld.glist;
+    const int SR = geo.short_rows;
+    const bool seg = p.opt.short_seg > 0 || (p.opt.short_seg == 0 && !f16 && !p.windowed);
+    int seg_max_len = 4;          // the longest rows that take the segmented layout
+    if (seg && p.opt.short_seg == 0 && !meta_only && nnz_short <= (16ll << 20)) {
+        // r6 (tests/test_zz_auto_rules.py, tools/category_sweep.py): in a slab a lane owns whole rows, so the 64 lanes of a step gather for 128 neighbouring rows of one
+        // length -- where neighbouring short rows read neighbouring columns (road networks, meshes' boundary rows) those gathers coalesce, and while the launch is
+        // latency-bound the slabs win: rows of 1..4 within +-64 columns of the diagonal, 262 k / 1 M / 4 M rows: 4.9 / 15.5 / 50.2 us segmented against 3.9 / 12.3 / 46.9
+        // as slabs.  At HBM scale the segmented tiles (256 elements per wave against 128 L) are the faster stream again (16 M rows: 219 against 192 us; 24 M: 356 / 325
+        // with slabs for lengths 3 and 4 only) -- hence the bound of 16 M short nonzeros.  Graph rows (webbase-1M f64: 30.6 -> 28.4 us segmented) keep the segmented
+        // tiles at every size.  The measure of the slab rule above -- pairs of successive rows of one length -- with a wider test: positions whose columns differ by < 256
+        // (a tile's 128 rows then read a few KB of x: L1 hits, whatever the order inside)
+        std::vector<int> pairs;
+        for (int g = 0; g < 4; ++g) {
+            const std::vector<int> &list = *glist[g];
+            const int step = std::max(2, ((int)list.size() / 2048) & ~1);
+            for (size_t i = 0; i + 1 < list.size(); i += (size_t)step) { pairs.push_back(list[i]); pairs.push_back(list[i + 1]); }
+        }
+        long long near = 0, entries = 0;
+        if (int rc = bld.probe().row_coherence(pairs, 256, &near, &entries)) return rc;
+        if (entries >= 256 && 2 * near >= entries) seg_max_len = 0;
+    }
+    long long off = 0; int tile0 = 0;
+    for (int g = 0; g < kNumShortGroups; ++g) {
+        ShortGroup &G = p.grp[g];
+        G.seg = seg && !p.windowed && G.len >= 1 && G.len <= seg_max_len && g < 5 ? 1 : 0;
+        G.rpt = G.seg ? short_seg_rows(G.len) : SR;
+        G.tiles = ceil_div(G.count, G.rpt);
+        G.tile0 = tile0; G.elem_off = off;
+        tile0 += G.tiles;
+        off += (long long)G.tiles * short_tile_elems(G.seg != 0, G.len, SR);
+    }
+    if (off >= (1LL << 40)) { set_error("short segment too large"); return DASP_ERR_ARG; }
+    p.cnt_short = (size_t)off;
+    if (pack) {
+    p.short_val.resize((size_t)off * sizeof(T));           // not zero-filled: only a slab's last tile has pads
+    p.short_cid.resize((size_t)off);
+    if (p.value_map) p.short_map.assign((size_t)off, 0u);      // pads stay 0
+    T *sv = reinterpret_cast<T *>(p.short_val.data());
+    for (int g = 0; g < kNumShortGroups; ++g) {
+        const ShortGroup &G = p.grp[g];
+        if (G.tiles == 0 || G.len == 0) continue;
+        // pads: a slab's last tile only; a segmented group of 3 has an idle lane in every 16, so all of it is cleared first
+        const size_t te = (size_t)short_tile_elems(G.seg != 0, G.len, SR);
+        const size_t t0 = (size_t)G.elem_off + (G.seg && G.len == 3 ? 0 : (size_t)(G.tiles - 1) * te), t1 = (size_t)G.elem_off + (size_t)G.tiles * te;
+        std::fill(sv + t0, sv + t1, (T)0);
+        std::fill(p.short_cid.begin() + t0, p.short_cid.begin() + t1, -1);
+    }
+    for (int g = 0; g < kNumShortGroups; ++g) {
+        const ShortGroup &G = p.grp[g];
+        if (G.len == 0 || G.count == 0) continue;
+        const std::vector<int> &list = *glist[g];
+        parallel_for(G.count, threads, 1 << 14, [&](long long b, long long e) {
+            for (long long t = b; t < e; ++t) {
+                const int row = list[t], a0 = rp[row];
+                for (int k = 0; k < G.len; ++k) {
+                    const size_t at = (size_t)G.elem_off + short_elem_index(G.seg != 0, G.len, SR, t, k);
+                    sv[at] = val[a0 + k];
+                    if (p.value_map) p.short_map[at] = map_entry(p, a0 + k);
+                    p.short_cid[at] = remap(ci[a0 + k]);
                 }
             }
         });
     }
+    }   // pack
 
-    lap("pack medium");
-    // ---- short rows: one slab per length, tile-major [tile][k][short_rows] -- or, for the rows of 1..4 nonzeros, the wave-segmented layout
-    // (opt.short_seg, plan.hpp short_elem_index): auto = f64 plans without x windows (the windowed kernels are held to 64 registers and
-    // spill more with the DPP path compiled in: cop20k_A 11.1 -> 12.0 us; f16 gains nothing: DESIGN.md section 3)
-    {
-        const int SR = geo.short_rows;
-        const bool seg = p.opt.short_seg > 0 || (p.opt.short_seg == 0 && !f16 && !p.windowed);
-        int seg_max_len = 4;          // the longest rows that take the segmented layout
-        if (seg && p.opt.short_seg == 0 && !meta_only && nnz_short <= (16ll << 20)) {
-            // r6 (tests/test_zz_auto_rules.py, tools/category_sweep.py): in a slab a lane owns whole rows, so the 64 lanes of a step gather for 128 neighbouring rows of one
-            // length -- where neighbouring short rows read neighbouring columns (road networks, meshes' boundary rows) those gathers coalesce, and while the launch is
-            // latency-bound the slabs win: rows of 1..4 within +-64 columns of the diagonal, 262 k / 1 M / 4 M rows: 4.9 / 15.5 / 50.2 us segmented against 3.9 / 12.3 / 46.9
-            // as slabs.  At HBM scale the segmented tiles (256 elements per wave against 128 L) are the faster stream again (16 M rows: 219 against 192 us; 24 M: 356 / 325
-            // with slabs for lengths 3 and 4 only) -- hence the bound of 16 M short nonzeros.  Graph rows (webbase-1M f64: 30.6 -> 28.4 us segmented) keep the segmented
-            // tiles at every size.  The measure of the slab rule above -- pairs of successive rows of one length -- with a wider test: positions whose columns differ by < 256
-            // (a tile's 128 rows then read a few KB of x: L1 hits, whatever the order inside)
-            std::vector<int> pairs;
-            for (int g = 0; g < 4; ++g) {
-                const std::vector<int> &list = *glist[g];
-                const int step = std::max(2, ((int)list.size() / 2048) & ~1);
-                for (size_t i = 0; i + 1 < list.size(); i += (size_t)step) { pairs.push_back(list[i]); pairs.push_back(list[i + 1]); }
-            }
-            long long near = 0, entries = 0;
-            if (dev) { if (int rc = devpack_row_coherence(p, *dev, pairs, 256, &near, &entries)) return rc; }
-            else
-                for (size_t q = 0; q + 1 < pairs.size(); q += 2) {
-                    const int a = rp[pairs[q]], b = rp[pairs[q + 1]], len = rp[pairs[q] + 1] - a;
-                    for (int k = 0; k < len; ++k) { const int d = remap(ci[a + k]) - remap(ci[b + k]); near += d > -256 && d < 256; }
-                    entries += len;
-                }
-            if (entries >= 256 && 2 * near >= entries) seg_max_len = 0;
-        }
-        long long off = 0; int tile0 = 0;
-        for (int g = 0; g < kNumShortGroups; ++g) {
-            ShortGroup &G = p.grp[g];
-            G.seg = seg && !p.windowed && G.len >= 1 && G.len <= seg_max_len && g < 5 ? 1 : 0;
-            G.rpt = G.seg ? short_seg_rows(G.len) : SR;
-            G.tiles = ceil_div(G.count, G.rpt);
-            G.tile0 = tile0; G.elem_off = off;
-            tile0 += G.tiles;
-            off += (long long)G.tiles * short_tile_elems(G.seg != 0, G.len, SR);
-        }
-        if (off >= (1LL << 40)) { set_error("short segment too large"); return DASP_ERR_ARG; }
-        p.cnt_short = (size_t)off;
-        if (pack) {
-        p.short_val.resize((size_t)off * sizeof(T));           // not zero-filled: only a slab's last tile has pads
-        p.short_cid.resize((size_t)off);
-        if (p.value_map) p.short_map.assign((size_t)off, 0u);      // pads stay 0
-        T *sv = reinterpret_cast<T *>(p.short_val.data());
-        for (int g = 0; g < kNumShortGroups; ++g) {
-            const ShortGroup &G = p.grp[g];
-            if (G.tiles == 0 || G.len == 0) continue;
-            // pads: a slab's last tile only; a segmented group of 3 has an idle lane in every 16, so all of it is cleared first
-            const size_t te = (size_t)short_tile_elems(G.seg != 0, G.len, SR);
-            const size_t t0 = (size_t)G.elem_off + (G.seg && G.len == 3 ? 0 : (size_t)(G.tiles - 1) * te), t1 = (size_t)G.elem_off + (size_t)G.tiles * te;
-            std::fill(sv + t0, sv + t1, (T)0);
-            std::fill(p.short_cid.begin() + t0, p.short_cid.begin() + t1, -1);
-        }
-        for (int g = 0; g < kNumShortGroups; ++g) {
-            const ShortGroup &G = p.grp[g];
-            if (G.len == 0 || G.count == 0) continue;
-            const std::vector<int> &list = *glist[g];
-            parallel_for(G.count, threads, 1 << 14, [&](long long b, long long e) {
-                for (long long t = b; t < e; ++t) {
-                    const int row = list[t], a0 = rp[row];
-                    for (int k = 0; k < G.len; ++k) {
-                        const size_t at = (size_t)G.elem_off + short_elem_index(G.seg != 0, G.len, SR, t, k);
-                        sv[at] = val[a0 + k];
-                        if (p.value_map) p.short_map[at] = map_entry(p, a0 + k);
-                        p.short_cid[at] = remap(ci[a0 + k]);
-                    }
-                }
-            });
-        }
-        }   // pack
-    }
+    bld.lap("pack short");
+    return DASP_OK;
+}
 
-    lap("pack short");
-    // ---- stats: the reference's CSV counters (dasp_f64.h:1439-1441) + native sizes
+// ---- stats: the reference's CSV counters (dasp_f64.h:1439-1441) + native sizes
+template <class T> static int fill_stats(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    const Geometry &geo = bld.geo;
+    const RefGeometry &refg = bld.refg;
+    const int m = bld.m, nnz = bld.nnz, n1 = bld.n1, n2 = bld.n2, n3 = bld.n3, n4 = bld.n4, nz0 = bld.nz0, c13 = bld.c13, nsp = bld.nsp;
+    const int row_long = bld.row_long, row_block = bld.row_block, mfma_rows = bld.mfma_rows, nb = bld.nb;
+    const int nnz_short = bld.nnz_short, nnz_irreg = bld.nnz_irreg;
+    const long long nnz_long = bld.nnz_long, n_reg = bld.n_reg;
+    const bool natural = bld.natural;
+    const double window_frac = bld.window_frac;
     dasp_stats_t &s = p.stats;
     std::memset(&s, 0, sizeof s);
     s.precision = p.precision; s.rowA = m; s.colA = p.n; s.nnzA = nnz;
     s.short_row_1 = n1; s.common_13 = c13; s.short_row_3 = n3; s.short_row_4 = n4; s.short_row_2 = n2;
     s.short_seg = 0;
     for (int g = 0; g < kNumShortGroups; ++g) s.short_seg |= p.grp[g].seg;
-    s.row_long = nlong_cls; s.row_block = nmed_all; s.row_zero = nz0; s.med_rows_as_pieces = nsp; s.chunk_pairs = p.pair_mode; s.cid8_chunks = p.med_c8ptr.empty() ? 0 : p.med_c8ptr.back();
+    s.row_long = row_long; s.row_block = row_block; s.row_zero = nz0; s.med_rows_as_pieces = nsp; s.chunk_pairs = p.pair_mode; s.cid8_chunks = p.med_c8ptr.empty() ? 0 : p.med_c8ptr.back();
     s.nnz_short = nnz_short; s.nnz_long = (int)nnz_long; s.nnz_irreg = nnz_irreg;
     s.origin_nnz_reg = nnz - nnz_irreg - (int)nnz_long - nnz_short;
-    s.rowloop = nmed < 59990 ? 1 : (nmed < 400000 ? 2 : 4);
+    s.rowloop = mfma_rows < 59990 ? 1 : (mfma_rows < 400000 ? 2 : 4);
     s.fill0_nnz_short = (long long)p.cnt_short;
     s.fill0_nnz_long = (long long)p.cnt_long;
     s.fill0_nnz_reg = n_reg;
@@ -1379,21 +1728,80 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
     s.window_nnz_frac = window_frac;
     s.x_window_hybrid = p.win_hybrid ? 1 : 0;
     if (p.windowed) { const int wpw = std::min(16, p.row_window / kMedRows); s.n_workgroups = ceil_div(s.n_long_pieces, wpw) + ceil_div(s.n_windows, 8) * 8 + (win_fold_tiles(s.n_windows, s.n_short_tiles) ? 0 : ceil_div(s.n_short_tiles, wpw)); }
-    if (dev && !meta_only) {   // the O(nnz) copies happen on the GPU; the plan comes back uploaded
+    return DASP_OK;
+}
+
+// the tail: a device CSR is packed on the GPU from the tables built above; a metadata-only plan gives up what the panels / the tile streams own
+template <class T> static int finish(Build<T> &bld)
+{
+    Plan &p = bld.p;
+    if (bld.dev && !bld.meta_only) {   // the O(nnz) copies happen on the GPU; the plan comes back uploaded
         PackMeta meta;
-        meta.ridL = &ridL; meta.startL = &startL; meta.ridM = &ridM; meta.lenM = &lenM;
-        for (int g = 0; g < kNumShortGroups; ++g) meta.glist[g] = glist[g];
-        if (int rc = devpack_all(p, *dev, meta)) return rc;
-        lap("device pack");
+        meta.ridL = &bld.ridL; meta.startL = &bld.startL; meta.ridM = &bld.ridM; meta.lenM = &bld.lenM;
+        for (int g = 0; g < kNumShortGroups; ++g) meta.glist[g] = bld.glist[g];
+        if (int rc = devpack_all(p, *bld.dev, meta)) return rc;
+        bld.lap("device pack");
     }
-    if (meta_only) {   // the panels own the packed data; this plan keeps order_rid + the whole-matrix counters
+    if (bld.meta_only) {   // the panels own the packed data; this plan keeps order_rid + the whole-matrix counters
         p.cnt_long = p.cnt_reg = p.cnt_irr = p.cnt_short = 0;
         p.piece_ptr.clear(); p.piece_dst.clear(); p.multi_ptr.clear(); p.multi_dst.clear(); p.piece_c16.clear(); p.long_base.clear(); p.long_cid16.clear(); p.cnt_long_chunks = 0;
         p.med_ptr.clear(); p.irr_ptr.clear();
         for (int g = 0; g < kNumShortGroups; ++g) { p.grp[g].tiles = 0; p.grp[g].tile0 = 0; p.grp[g].elem_off = 0; }
     }
-    s.pre_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    p.stats.pre_ms = bld.lap.ms();
     return DASP_OK;
+}
+
+// ---- the DASP form, stage by stage: every stage reads what the ones before it left in the state and in the plan
+template <class T> static int run_stages(Build<T> &bld)
+{
+    int (*const stages[])(Build<T> &) = {classify_rows<T>, sort_medium_by_length<T>, measure_reference<T>, assign_slots<T>, decide_windows<T>, medium_rows_as_pieces<T>,
+                                         pack_long<T>, split_medium_chunks<T>, pack_medium<T>, pack_short<T>, fill_stats<T>, finish<T>};
+    for (auto stage : stages)
+        if (int rc = stage(bld)) return rc;
+    return DASP_OK;
+}
+
+// the DASP form of a CSR that needs no entry work: the metadata of a whole matrix (order_rid + counters; dev = nullptr, ci and val are not read), or one column panel
+template <class T> static int build_dasp(Plan &p, const int *rp, const int *ci, const T *val, const DevCsr *dev, bool meta_only)
+{
+    Build<T> bld(p, rp, ci, val, dev, meta_only);
+    if (!row_ptr_ends_ok(rp, bld.m, bld.nnz)) return DASP_ERR_ARG;
+    bld.lap("validate");
+    return run_stages(bld);
+}
+
+// ---- which form a whole plan takes: the entry work (validate, sort the columns), then the two-phase / hybrid form where its rule asks for it, column panels where
+// theirs does, else the plain DASP form
+template <class T> static int build_form(Plan &p, const int *rp, const int *ci_in, const T *val_in, const DevCsr *dev_in)
+{
+    Build<T> bld(p, rp, ci_in, val_in, dev_in, false);
+    if (int rc = validate_csr(bld)) return rc;
+    SortedCsr<T> sorted;
+    struct MapSrcReset { Plan &q; ~MapSrcReset() { q.map_src = nullptr; } } map_src_reset{p};      // map_src never outlives the top-level build
+    if (int rc = sort_columns(bld, sorted)) return rc;
+    int scattered = 0;
+    const int P = decide_panels(p, bld.probe(), &scattered);
+    if (P < 0) return P;
+    if (decide_two_phase(p, rp, scattered)) {
+        // the two-phase (gather-free) form: order_rid and the classifier counters of the whole matrix (row lengths only), then the tile streams
+        if (int rc = build_dasp<T>(p, rp, bld.ci, bld.val, nullptr, true)) return rc;
+        bld.lap("whole-matrix meta");
+        int rc2;
+        if (!bld.dev) { rc2 = hybrid_then_tp(bld, bld.ci, bld.val); bld.lap("two-phase streams"); if (rc2 != kTpDeclined) return rc2; }
+        else {
+            rc2 = devpack_forms_enabled() ? hybrid_then_tp_device(bld) : kDevNoScratch;
+            if (rc2 == kDevNoScratch) {
+                rc2 = hybrid_then_tp_fetched(bld);
+                if (rc2 == DASP_OK) return devpack_finish_panels(p);       // a device-built plan comes back uploaded
+            }
+            if (rc2 == DASP_OK) return DASP_OK;
+            if (rc2 != kTpDeclined) return rc2;
+        }
+        // declined by the padding guard (automatic rule only): the matrix keeps its DASP form -- column panels where the rule asked for them, else the plain plan below
+    }
+    if (P >= 2) return build_panels<T>(p, rp, bld.ci, bld.val, P, bld.dev);
+    return run_stages(bld);
 }
 
 // ---- column panels (opt.col_panels; DESIGN.md section 4 "column panels") -------------------------------------------------
@@ -1401,8 +1809,9 @@ static int build_impl(Plan &p, const int *rp, const int *ci, const T *val, const
 // locality (FEM / stencil rows touch runs of neighbouring columns, banded rows stay inside a narrow span) is left alone.
 // *scattered (r5; what the two-phase rule asks): 1 when a matrix of >= 10 M nonzeros has rows whose gathers scatter -- > 50 % of a sampled row's nonzeros on distinct
 // 128-byte lines of x, a third of the entries in rows spanning > x / 4 -- whatever the size of x and however hot some of its lines are
-static int decide_panels(const Plan &p, const int *rp, const int *ci, const Remap &remap, const DevCsr *dev, int *scattered)
+static int decide_panels(const Plan &p, const CsrProbe &probe, int *scattered)
 {
+    const int *rp = probe.rp;
     if (scattered) *scattered = 0;
     const int want = p.opt.col_panels;
     if (want > 64) { set_error("col_panels must be <= 64"); return DASP_ERR_ARG; }
@@ -1435,25 +1844,17 @@ static int decide_panels(const Plan &p, const int *rp, const int *ci, const Rema
     std::vector<long long> core_spans;          // per sampled row: 10th to 90th percentile of its columns
     std::vector<int> cols;
     // device CSR (r3): the sampled rows' column ids are gathered by a kernel and copied over (<= 2 M ids), the rule itself is the same
-    std::vector<int> fetched;
-    if (dev) {
-        std::vector<long long> idx;
-        for (int s = 0; s < S; ++s) {
-            const int r = (int)((long long)p.m * s / S), len = rp[r + 1] - rp[r];
-            if (len < 4) continue;
-            for (int j = 0; j < std::min(len, 512); ++j) idx.push_back((long long)rp[r] + j);
-        }
-        if (int rc = devpack_gather_columns(p, *dev, &idx, 0, 0, 0, fetched)) return rc;
-    }
-    size_t fpos = 0;
+    std::vector<int> rows, fetched;          // the sampled rows of >= 4 nonzeros; the first 512 column ids of each
     for (int s = 0; s < S; ++s) {
         const int r = (int)((long long)p.m * s / S);
-        const int len = rp[r + 1] - rp[r];
-        if (len < 4) continue;
-        const int take = std::min(len, 512);
-        cols.resize((size_t)take);
-        if (dev) { for (int j = 0; j < take; ++j) cols[j] = fetched[fpos + (size_t)j]; fpos += (size_t)take; }
-        else for (int j = 0; j < take; ++j) cols[j] = remap(ci[rp[r] + j]);
+        if (rp[r + 1] - rp[r] >= 4) rows.push_back(r);
+    }
+    if (int rc = probe.columns_of_rows(rows, 512, fetched)) return rc;
+    size_t fpos = 0;
+    for (int r : rows) {
+        const int take = std::min(rp[r + 1] - rp[r], 512);
+        cols.assign(fetched.begin() + (long long)fpos, fetched.begin() + (long long)(fpos + (size_t)take));
+        fpos += (size_t)take;
         std::sort(cols.begin(), cols.end());
         int distinct = 1;
         for (int j = 1; j < take; ++j) distinct += (cols[j] >> line_shift) != (cols[j - 1] >> line_shift);
@@ -1491,12 +1892,8 @@ static int decide_panels(const Plan &p, const int *rp, const int *ci, const Rema
         std::vector<int> hist((size_t)xlines, 0);
         const long long S2 = std::min<long long>(p.nnz, 1ll << 21), stride = std::max<long long>(1, p.nnz / S2);
         long long taken = 0;
-        if (dev) {
-            const long long cnt = (p.nnz + stride - 1) / stride;
-            if (int rc = devpack_gather_columns(p, *dev, nullptr, 0, stride, cnt, fetched)) return rc;
-            for (int c : fetched) { hist[(size_t)(c >> line_shift)]++; ++taken; }
-        } else
-        for (long long j = 0; j < p.nnz; j += stride) { hist[(size_t)(remap(ci[j]) >> line_shift)]++; ++taken; }
+        if (int rc = probe.columns_strided(stride, fetched)) return rc;
+        for (int c : fetched) { hist[(size_t)(c >> line_shift)]++; ++taken; }
         const size_t cap = (size_t)((3ll << 20) / 128);
         long long hot = 0;
         if (hist.size() > cap) {
@@ -1519,13 +1916,9 @@ template <class T>
 static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int P, const DevCsr *dev)
 {
     const DevCsr *const dev_in = dev;       // (the fallback of the hub rows' device packer fetches the CSR and splits it on the host: see long_cb below)
-    using clk = std::chrono::steady_clock;
-    const auto t_begin = clk::now();
-    const bool verbose = std::getenv("DASP_VERBOSE") != nullptr;
-    auto tick = t_begin;
-    auto lap = [&](const char *what) { if (verbose) { auto now = clk::now(); std::fprintf(stderr, "[dasp panels] %-26s %.3f s\n", what, std::chrono::duration<double>(now - tick).count()); tick = now; } };
+    LapTimer lap("[dasp panels] %-26s %.3f s\n");
     // whole-matrix classification: order_rid and the reference's counters are those of the unsplit matrix (row lengths only)
-    if (int rc = build_impl<T>(p, rp, ci, val, nullptr, kMetaOnly)) return rc;
+    if (int rc = build_dasp<T>(p, rp, ci, val, nullptr, true)) return rc;
     lap("whole-matrix meta");
     const int m = p.m;
     const int threads = resolve_threads(p.opt.host_threads);
@@ -1564,7 +1957,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
             lcb_ci.resize((size_t)p.nnz); lcb_val.resize((size_t)p.nnz);
             if (int rc = devpack_fetch_csr(p, *dev, lcb_ci.data(), lcb_val.data())) return rc;
             p.csr_fetch_bytes += (long long)p.nnz * (4 + (long long)sizeof(T));
-            if (p.value_map && dev->src) {      // (see the two-phase fetch in build_impl)
+            if (p.value_map && dev->src) {      // (see the two-phase fetch in hybrid_then_tp_fetched)
                 lcb_src.resize((size_t)p.nnz);
                 if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(lcb_src.data()), nullptr)) return rc;
                 p.csr_fetch_bytes += (long long)p.nnz * 4;
@@ -1693,7 +2086,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
                     }
                     // f16 only: 2-byte stores are where the partial lines hurt (ljournal-2008-uniform 0.590 -> 0.559 ms, ljournal-2008 0.506 -> 0.503; powerlaw_1M f64 0.651 -> 0.654)
                     if (!natural && p.precision == 16 && !ab_knobs().panel_row_scan) q.scan_order = p.order.data();      // (DASP_PANEL_ROW_SCAN: A/B knob, the r3 order)
-                    try { rcs[k] = build_impl<T>(q, rpP[k].data(), dev ? nullptr : ciP[k].data(), dev ? nullptr : valP[k].data(), dev ? &devP[(size_t)k] : nullptr, kPanel); }
+                    try { rcs[k] = build_dasp<T>(q, rpP[k].data(), dev ? nullptr : ciP[k].data(), dev ? nullptr : valP[k].data(), dev ? &devP[(size_t)k] : nullptr, false); }
                     catch (const std::bad_alloc &) { rcs[k] = DASP_ERR_NOMEM; set_error("out of host memory"); }
                     if (rcs[k] == DASP_OK && dev && q.cnt_rt > 0) rcs[k] = devpack_place_row_tiles(q, rt_dev[(size_t)k]);
                     if (rcs[k] != DASP_OK) { errs[k] = last_error_cstr(); continue; }
@@ -1759,7 +2152,7 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     if (dev && lcb_on) { if (int rc = devpack_finish_panels_lcb(p, *dev, lcb_pieces)) return rc; }
     else if (dev_in) { if (int rc = devpack_finish_panels(p)) return rc; }
     lap("parent upload");
-    s.pre_ms = std::chrono::duration<double, std::milli>(clk::now() - t_begin).count();
+    s.pre_ms = lap.ms();
     return DASP_OK;
 }
 
@@ -1767,8 +2160,8 @@ int build_plan(Plan &p, const int *rp, const int *ci, const void *val, const Dev
 {
     p.geo = geometry_for(p.precision);
     p.value_map = p.opt.value_map == 1;
-    if (p.precision == 64) return build_impl<double>(p, rp, ci, static_cast<const double *>(val), dev);
-    return build_impl<_Float16>(p, rp, ci, static_cast<const _Float16 *>(val), dev);
+    if (p.precision == 64) return build_form<double>(p, rp, ci, static_cast<const double *>(val), dev);
+    return build_form<_Float16>(p, rp, ci, static_cast<const _Float16 *>(val), dev);
 }
 
 }  // namespace dasp

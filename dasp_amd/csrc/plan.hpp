@@ -453,7 +453,7 @@ int devpack_sort_columns(const Plan &p, const DevCsr &d, std::vector<std::shared
 // ci / val are ignored and the nnz-sized arrays are produced on the device (the plan comes back uploaded).
 int build_plan(Plan &p, const int *rp, const int *ci, const void *val, const DevCsr *dev = nullptr);
 
-// two-phase form (twophase.cpp): the automatic rule (1: use it), the packer (after build_impl's meta pass: p.order / p.stats are set) and the
+// two-phase form (twophase.cpp): the automatic rule (1: use it), the packer (after the meta pass of build_form, plan.cpp: p.order / p.stats are set) and the
 // checks a loaded plan file must pass
 int decide_two_phase(const Plan &p, const int *rp, int scattered);
 // windowed plans: the workgroup's dynamic LDS = the window's copy of x (Plan::lds_bytes, a multiple of 256, <= kWinLdsMax); the kernels keep a word of static LDS beside it

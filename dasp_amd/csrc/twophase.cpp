@@ -173,7 +173,7 @@ int build_two_phase(Plan &p, const int *rp, const int *ci, const void *val, cons
     const int n_rb = t.n_rb();
     // the automatic rule's last word: every non-empty (row block, column block) tile is padded to whole 64-element segments, and a row block holds at most
     // rbm rows -- a large, very sparse matrix (50 M rows of 3 nonzeros: 1526 column blocks, ~8 nonzeros per tile) would store several times its nonzeros and keep
-    // n_rb * n_cb * 20 bytes of tables on the host.  Declined (kTpDeclined: build_impl goes on to column panels / the plain plan) when the padded streams pass 3 x the
+    // n_rb * n_cb * 20 bytes of tables on the host.  Declined (kTpDeclined: build_form goes on to column panels / the plain plan) when the padded streams pass 3 x the
     // nonzeros (webbase-1M x4, 1.59 x padding, wins 53.0 against 61.5 us; x16, 2.69 x, 291.9 against 328.2 us; the form's time follows its padded size, so ~3 x is the break-even there) or the tile table passes 64 M entries; a forced two_phase = 1 is built as asked.
     const bool may_decline = p.opt.two_phase == 0;
     if (may_decline && (long long)n_rb * (long long)n_cb > (1ll << 26)) { t = TwoPhase{}; return kTpDeclined; }

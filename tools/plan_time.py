@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/plan_time.py <workload> <precision> [scale=1] [opt=value ...] -- one plan of a stand-in through the Python mirror: all-ones exact check, event-timed ms, fraction of the
-8 TB/s roofline.  Honours DASP_AMD_SO (another build of the library), so two builds can be compared without LD_PRELOAD:  DASP_AMD_SO=dasp_amd/variants/<tag>/libdasp_amd.so python tools/plan_time.py ..."""
+8 TB/s roofline, and the plan's creation time (pre_ms).  Honours DASP_AMD_SO (another build of the library), so two builds can be compared without LD_PRELOAD:  DASP_AMD_SO=dasp_amd/variants/<tag>/libdasp_amd.so python tools/plan_time.py ..."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +27,6 @@ else:      # f16 results: rounded beyond 2048, +inf beyond 65504
     ok = bool(torch.where(want > 65504.0, torch.isinf(got) | fine, fine).all().item())
 st = plan.stats
 b_alg = ci.size * (prec // 8 + 4) + (m + 1) * 4 + (n + m) * (prec // 8)
-print("%s f%d %s | %.4f ms = %.3f of the roofline | two_phase %d panels %d fill0 %.4f narrow chunks %d, %.3f B/nnz packed | %s | %s" % (name, prec, kw, e, b_alg / (e * 1e6) / 8000, st["two_phase"], st["n_col_panels"], st["rate_fill0"],
-      st["cid8_chunks"], st["data_X"] / max(1, ci.size),
+print("%s f%d %s | %.4f ms = %.3f of the roofline | two_phase %d panels %d fill0 %.4f narrow chunks %d, %.3f B/nnz packed | pre_ms %.1f | %s | %s" % (name, prec, kw, e, b_alg / (e * 1e6) / 8000, st["two_phase"], st["n_col_panels"], st["rate_fill0"],
+      st["cid8_chunks"], st["data_X"] / max(1, ci.size), st["pre_ms"],
       "exact" if ok else "WRONG", os.environ.get("DASP_AMD_SO", "product")))
