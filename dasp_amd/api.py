@@ -331,6 +331,23 @@ class Plan:
         f = _lib.lib().dasp_plan_spmv_acc if accumulate else _lib.lib().dasp_plan_spmv
         _lib.check(f(self._h, C.c_void_p(dX), C.c_void_p(dY), C.c_void_p(stream)))
 
+    def set_f32_vectors(self, on):
+        """f32 vectors for an uploaded f16 two-phase plan on (1) / off (0) (dasp_plan_set_f32_vectors): 1 allocates the wide xs stream (and a hybrid's f64 hub
+        partials) that spmv_f32 needs, 0 frees them.  Allocates and synchronises: not inside a stream capture."""
+        _lib.check(_lib.lib().dasp_plan_set_f32_vectors(self._h, int(on)))
+
+    @property
+    def f32_vectors(self):
+        """1 for a two-phase plan whose spmv_f32 is ready, else 0."""
+        return int(_lib.lib().dasp_plan_f32_vectors(self._h))
+
+    def spmv_f32(self, dX, dY, stream=0, accumulate=False):
+        """y = A x with the f16 matrix of a two-phase plan and float32 vectors (dasp_plan_spmv_f32; accumulate: dasp_plan_spmv_acc_f32).  dX, dY: integer device
+        addresses of x_len / rowA float32 values; needs set_f32_vectors(1)."""
+        f = _lib.lib().dasp_plan_spmv_acc_f32 if accumulate else _lib.lib().dasp_plan_spmv_f32
+        fp = C.POINTER(C.c_float)
+        _lib.check(f(self._h, C.cast(C.c_void_p(dX), fp), C.cast(C.c_void_p(dY), fp), C.c_void_p(stream)))
+
     def time(self, dX, dY, stream=0, warmup=100, iters=1000):
         """The reference's protocol (dasp_f64.h:1285-1320): returns (wall_ms, event_ms) per SpMV."""
         w, e = C.c_double(), C.c_double()

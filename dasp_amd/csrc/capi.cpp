@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "plan.hpp"
+#include "device.hpp"
 #include "tp_exact.hpp"
 
 namespace dasp {
@@ -414,6 +415,41 @@ int dasp_tp_exact_dot_f16(const uint16_t *a, const uint16_t *x, long long n, int
     *y_out = tpx::dot_f16(a, x, n, accumulate == 1, y_in);
     return DASP_OK;
 }
+
+// f32 vectors over an f16 two-phase plan.  The checks that need no GPU come first, in the header's order; the allocations are upload.cpp's
+int dasp_plan_set_f32_vectors(dasp_plan_t *plan, int on)
+{
+    if (!plan) { set_error("dasp_plan_set_f32_vectors: null plan"); return DASP_ERR_ARG; }
+    Plan &p = plan->impl;
+    if (on != 0 && on != 1) { set_error("f32_vectors must be 0 or 1"); return DASP_ERR_ARG; }
+    if (p.panel) { set_error("dasp_plan_set_f32_vectors: a borrowed panel handle"); return DASP_ERR_ARG; }
+    if (p.precision != 16 || !p.two_phase || p.stats.two_phase != 1) {
+        set_error("f32 vectors need an f16 plan in the two-phase form (dasp_stats_t::two_phase == 1): dasp_options_t::two_phase = 1 forces that form for any f16 matrix without a column remap");
+        return DASP_ERR_ARG;
+    }
+    if ((size_t)p.tp.cb * 4 > 160 * 1024) {
+        set_error("f32 vectors: tp_col_block = " + std::to_string(p.tp.cb) + " is more than 40960 columns -- the f32 slice of x of one column block must fit the 160 KiB of LDS of one CU");
+        return DASP_ERR_ARG;
+    }
+    if (p.lcb.n_rows() > 0 && (size_t)p.lcb.cb * 4 + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 8 > 160 * 1024) {
+        set_error("f32 vectors: the hub rows' column block of " + std::to_string(p.lcb.cb) + " columns does not fit the LDS as f32");
+        return DASP_ERR_ARG;
+    }
+    if (!p.dev || !p.dev->arena) { set_error("dasp_plan_set_f32_vectors: plan not uploaded"); return DASP_ERR_STATE; }
+    return guarded("dasp_plan_set_f32_vectors", [&] { return set_f32_vectors_device(p, on); });
+}
+
+int dasp_plan_f32_vectors(const dasp_plan_t *plan) { return plan && plan->impl.two_phase && plan->impl.f32_vectors ? 1 : 0; }
+
+static int spmv_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream, bool accumulate)
+{
+    if (!plan) { set_error("dasp_plan_spmv_f32: null plan"); return DASP_ERR_ARG; }
+    if (!plan->impl.f32_vectors) { set_error("f32 vectors are off: call dasp_plan_set_f32_vectors(plan, 1) on the uploaded two-phase plan first"); return DASP_ERR_STATE; }
+    if (!dX || !dY) { set_error("null device pointer"); return DASP_ERR_ARG; }
+    return launch_spmv_f32(plan->impl, dX, dY, stream, accumulate);
+}
+int dasp_plan_spmv_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream) { return spmv_f32(plan, dX, dY, stream, false); }
+int dasp_plan_spmv_acc_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream) { return spmv_f32(plan, dX, dY, stream, true); }
 
 int dasp_plan_spmv(dasp_plan_t *plan, const void *dX, void *dY, void *stream)
 {

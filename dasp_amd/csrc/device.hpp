@@ -110,6 +110,10 @@ struct DevicePlan {
     // an f16 two-phase plan with hub rows: what the exact hub kernels write and read (LcbDev::xpart), n_cb x n_rows x 20 bytes in an allocation of its own (the arena is
     // byte for byte the same with or without it), zero-filled at upload: empty (row, block) pieces are never written
     void *lcb_xpart = nullptr;
+    // f32 vectors over an f16 two-phase plan (dasp_plan_set_f32_vectors; Plan::f32_vectors): the xs stream of dasp_plan_spmv_f32, 4 bytes per stored element, and -- a
+    // hybrid only -- the hub rows' f64 partial sums, n_cb x n_rows x 8 bytes.  Two allocations of their own, zero-filled (empty (row, block) pieces are never written), made
+    // and freed by the setter: the arena is byte for byte the same with or without them.  The launch puts them in the places of TpDev::xs / LcbDev::partial
+    void *wide_xs = nullptr, *wide_part = nullptr;
     bool nt = false;
     bool win1 = false;      // windowed plan with at most one window workgroup per CU: launch dasp_spmv_win1_kernel
     // f64, no windows: most of the regular chunks sit in ONE-SHOT blocks (rows of <= 32: all of a block's loads in flight at once, a wave's life is two memory round
@@ -147,8 +151,10 @@ int sync_dev_args(Plan &p);            // upload.cpp: DevicePlan::dargs = Device
 int upload_plan_unpacked(Plan &p);     // for the device packers: arena + O(rows) arrays, no placement trials yet
 // kernels.hip: one SpMV of an uploaded plan (asynchronous); what upload.cpp asks the kernels
 int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate);
+int launch_spmv_f32(Plan &p, const float *dX, float *dY, void *stream, bool accumulate);      // kernels.hip: the same with f32 vectors (an f16 two-phase plan in f32-vector mode)
+int set_f32_vectors_device(Plan &p, int on);    // upload.cpp: makes / frees DevicePlan::wide_xs and wide_part of an uploaded two-phase plan and sets Plan::f32_vectors
 int spmv_kernel_allow_full_lds(int precision, bool c16);
-int tp_kernels_allow_lds();             // kernels.hip: the two-phase kernels may use up to 160 KiB of dynamic LDS (called at upload)
+int tp_kernels_allow_lds();             // kernels.hip: the two-phase kernels, the f32-vector ones included, may use up to 160 KiB of dynamic LDS (called at upload)
 int spmv_kernel_f16_resident(bool c16);
 int tune_placement(Plan &p, int trials, const void *dX, void *dY, double *ms_first, double *ms_kept);   // kernels.hip: placement trials of an uploaded, fully packed plan (trials <= 0: default)
 

@@ -626,6 +626,145 @@ __global__ __launch_bounds__(256) void dasp_lcb_reduce_exact_kernel(LcbDev a, _F
     }
 }
 
+// ------------------------------------------------------------------ f32 vectors over an f16 two-phase plan (dasp_plan_set_f32_vectors / dasp_plan_spmv_f32)
+// The packed streams do not depend on the vector type (val f16, lrow / lcol u16): only xs and the x / y accesses do.  Phase 1 is dasp_tp_expand_kernel<float> over a
+// wide xs of the plan's own (DevicePlan::wide_xs, 4 bytes per stored element; dynamic LDS cb x 4); the kernels below are phase 2 and the hub rows.  A product
+// (double)a x (double)x is exact (11 x 24 significant bits), sums are f64, the result is rounded ONCE: y = (float)d, or (float)((double)y_old + d).
+//
+// Phase 2: the grid, the three streams and both collision savers of dasp_tp_reduce_kernel; val as f16x8 (16 bytes), lrow as u16x8, xs as f32x8 (two 16-byte loads).
+__global__ __launch_bounds__(512) void dasp_tp_reduce_f32_kernel(TpDev a, float *__restrict__ y, int acc)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    typedef _Float16 vec8 __attribute__((ext_vector_type(8)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    double *yl = reinterpret_cast<double *>(lds_raw);
+    const int r = blockIdx.x;
+    const int p0 = a.rb_row0[r], rows = a.rb_row0[r + 1] - p0;
+    for (int i = threadIdx.x; i < rows; i += 512) yl[i] = 0.0;
+    __syncthreads();
+    const int s0 = a.rb_seg0[r], s1 = a.rb_seg0[r + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int LPS = kTpSeg / 8, SPW = 64 / LPS;
+    const int sub = lane / LPS, off = (lane % LPS) * 8;
+    const _Float16 *val = static_cast<const _Float16 *>(a.val);
+    const float *xs = static_cast<const float *>(a.xs);
+#pragma unroll 2
+    for (int g = s0 + wave * SPW; g < s1; g += 8 * SPW) {
+        const int seg = g + sub;
+        if (seg < s1) {
+            const size_t at = (size_t)seg * kTpSeg + off;
+            const vec8 v = __builtin_nontemporal_load(reinterpret_cast<const vec8 *>(val + at));
+            const tp_u16x8 lr = __builtin_nontemporal_load(reinterpret_cast<const tp_u16x8 *>(a.lrow + at));
+            const f32x4 x0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xs + at));
+            const f32x4 x1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xs + at + 4));
+            // the in-lane run: consecutive elements of one row are added in f64 first and cost one atomic (a pad's product -- value 0 x whatever its column block
+            // starts with, NaN where that is an infinity -- only ever joins a run of pads, which is dropped)
+            unsigned cur = lr[0];
+            double run = (double)v[0] * (double)x0[0];
+            bool one_run = true;
+#pragma unroll
+            for (int j = 1; j < 8; ++j) {
+                const unsigned r = lr[j];
+                const double p = (double)v[j] * (double)(j < 4 ? x0[j & 3] : x1[j & 3]);
+                if (r == cur) run += p;
+                else {
+                    if (cur != kTpPadRow) __hip_atomic_fetch_add(yl + cur, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    cur = r; run = p; one_run = false;
+                }
+            }
+            // ... and the segmented scan across the lanes of one segment, as in dasp_tp_reduce_kernel: one atomic per run of lanes that each hold one run of the same row
+            const unsigned key = one_run && cur != kTpPadRow ? cur : 0x10000u + (unsigned)lane;
+            const int ls = lane % LPS;
+#define DASP_TP_SCAN(D, CTRL) if constexpr (D < LPS) { const unsigned k2 = (unsigned)__builtin_amdgcn_update_dpp((int)key, (int)key, CTRL, 0xf, 0xf, false); const double r2 = dpp_mov_f64<CTRL>(run); if (ls >= D && k2 == key) run += r2; }
+            DASP_TP_SCAN(1, 0x111) DASP_TP_SCAN(2, 0x112) DASP_TP_SCAN(4, 0x114)
+#undef DASP_TP_SCAN
+            const unsigned knext = (unsigned)__builtin_amdgcn_update_dpp((int)key, (int)key, 0x101, 0xf, 0xf, false);       // row_shl:1
+            const bool last = ls == LPS - 1 || knext != key;
+            if (cur != kTpPadRow && last) __hip_atomic_fetch_add(yl + cur, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    __syncthreads();
+    if (acc) { for (int i = threadIdx.x; i < rows; i += 512) y[p0 + i] = (float)((double)y[p0 + i] + yl[i]); }
+    else for (int i = threadIdx.x; i < rows; i += 512) y[p0 + i] = (float)yl[i];
+}
+
+// The hub rows: the grid, units, 16-byte loads and U = 4 steps in flight of dasp_lcb_kernel<_Float16> over the same four lcb arrays; the block's slice of x is staged
+// as f32 (cb x 4 bytes), a step's 128 products are added in f64 (8 per lane, then the 16 lanes of the step by DPP) and parked in LDS, one thread per piece adds the
+// piece's step sums in order and writes an f64 partial (LcbDev::partial = DevicePlan::wide_part here): no atomics, a fixed order of addition.
+__global__ __launch_bounds__(1024) void dasp_lcb_f32_kernel(LcbDev a, const float *__restrict__ x)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    constexpr int A = 8;
+    typedef _Float16 vecA __attribute__((ext_vector_type(A)));
+    typedef unsigned short colA __attribute__((ext_vector_type(A)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    float *xl = reinterpret_cast<float *>(lds_raw);
+    const int u = blockIdx.x;
+    const int c = a.unit[3 * u], q0 = a.unit[3 * u + 1], q1 = a.unit[3 * u + 2];
+    const int c0 = c * a.cb, len = min(a.cb, a.xlen - c0);
+    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {          // (c0 is a multiple of 4 elements)
+        for (int i = threadIdx.x * 4; i < len; i += 1024 * 4) {
+            if (i + 4 <= len) *reinterpret_cast<f32x4 *>(xl + i) = *reinterpret_cast<const f32x4 *>(x + c0 + i);
+            else for (int j = i; j < len; ++j) xl[j] = x[c0 + j];
+        }
+    } else for (int i = threadIdx.x; i < len; i += 1024) xl[i] = x[c0 + i];
+    __syncthreads();
+    constexpr int G = kLcbStep / A, SPW = 64 / G;         // 16 lanes per step, four steps per wave instruction
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane / G, l = lane % G;
+    double *stepsum = reinterpret_cast<double *>(lds_raw + (((size_t)a.cb * 4 + 15) & ~size_t(15)));
+    const int np = q1 - q0;
+    const _Float16 *val = static_cast<const _Float16 *>(a.val);
+    const int S0 = a.ptr[q0] / kLcbStep, S1 = a.ptr[q1] / kLcbStep;
+    constexpr int U = 4;
+    for (int sb = S0 + wave * SPW * U; sb < S1; sb += 16 * SPW * U) {
+        vecA v[U]; colA lc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int st = min(sb + u * SPW + g, S1 - 1);          // (a step past the end re-reads the last one; its sum is dropped below)
+            const size_t e = (size_t)st * kLcbStep + (size_t)l * A;
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const vecA *>(val + e));
+            lc[u] = __builtin_nontemporal_load(reinterpret_cast<const colA *>(a.lcol + e));
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                const bool pad = lc[u][j] == kLcbPadCol;          // pads reach neither x nor the sum
+                const float xv = xl[pad ? 0 : lc[u][j]];
+                s += pad ? 0.0 : (double)v[u][j] * (double)xv;
+            }
+            s += dpp_mov_f64<0x128>(s); s += dpp_mov_f64<0x124>(s); s += dpp_mov_f64<0x122>(s); s += dpp_mov_f64<0x121>(s);      // row_ror 8, 4, 2, 1
+            if (l == 0 && sb + u * SPW + g < S1) stepsum[sb + u * SPW + g - S0] = s;
+        }
+    }
+    __syncthreads();
+    double *partial = static_cast<double *>(a.partial);
+    for (int i = threadIdx.x; i < np; i += 1024) {
+        double s = 0.0;
+        for (int st = a.ptr[q0 + i] / kLcbStep - S0, se = a.ptr[q0 + i + 1] / kLcbStep - S0; st < se; ++st) s += stepsum[st];
+        partial[q0 + i] = s;
+    }
+}
+// one workgroup per hub row: its n_cb f64 partials, thread-strided, summed per wave and then over the four waves through LDS -- a fixed order of addition -- and added
+// into y BEHIND phase 2 (which stored +0 there, or (float)((double)y_old + 0) in accumulate mode): y[dst] = (float)((double)y[dst] + s)
+__global__ __launch_bounds__(256) void dasp_lcb_reduce_f32_kernel(LcbDev a, float *__restrict__ y)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];          // dynamic: kWavesPerWG x 8 bytes
+    double *wsum = reinterpret_cast<double *>(lds_raw);
+    static_assert(kWavesPerWG == 4, "four waves per workgroup");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x;
+    const double *partial = static_cast<const double *>(a.partial);
+    double s = 0.0;
+    for (int c = threadIdx.x; c < a.n_cb; c += 256) s += partial[(size_t)c * (size_t)a.n_rows + (size_t)i];
+    s = wave_sum(s);
+    if (lane == 0) wsum[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) { const int d = a.row_dst[i]; y[d] = (float)((double)y[d] + ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]))); }
+}
+
 #ifdef DASP_STAMPS
 int g_stamp_launch = -1;          // host: the number the next stamped launch carries (-1: stamps off)
 }  // namespace dasp
@@ -778,7 +917,10 @@ int set_stream_policy(Plan &p, int policy)
 int tp_kernels_allow_lds()
 {
     for (const void *fn : {reinterpret_cast<const void *>(&dasp_tp_expand_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_tp_reduce_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_tp_reduce_exact_kernel),
-                           reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_lcb_kernel<double>), reinterpret_cast<const void *>(&dasp_lcb_exact_kernel)})
+                           reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_lcb_kernel<double>), reinterpret_cast<const void *>(&dasp_lcb_exact_kernel),
+                           // f32 vectors (dasp_plan_spmv_f32): an f32 slice of x is twice the f16 one
+                           reinterpret_cast<const void *>(&dasp_tp_expand_kernel<float>), reinterpret_cast<const void *>(&dasp_tp_reduce_f32_kernel), reinterpret_cast<const void *>(&dasp_lcb_f32_kernel),
+                           reinterpret_cast<const void *>(&dasp_lcb_reduce_f32_kernel)})
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return DASP_OK;
 }
@@ -886,6 +1028,30 @@ int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate
     if (const char *e = std::getenv("DASP_Y_WT")) a.ywt = a.ywt && std::atoi(e) != 0;      // A/B knob
     hipStream_t s = static_cast<hipStream_t>(stream);
     return p.precision == 64 ? launch_typed<double>(p, a, s) : launch_typed<_Float16>(p, a, s);
+}
+
+// y = (y +) A x with f32 vectors over an f16 two-phase plan (dasp_plan_spmv_f32): the launch order of the hybrid above -- hub stream kernel, phase 1, phase 2, hub
+// reduce -- over the same packed arrays.  The device views are built HERE from the plan's current ones (an arena moved by the placement trials is still found; refreshed
+// values are read from the same val), with the wide xs and the f64 hub partials (DevicePlan::wide_xs / wide_part) in the places of the f16 ones.
+int launch_spmv_f32(Plan &p, const float *dX, float *dY, void *stream, bool accumulate)
+{
+    if (!p.dev || !p.dev->arena) { set_error("plan not uploaded"); return DASP_ERR_STATE; }
+    if (!p.two_phase || !p.f32_vectors || !p.dev->wide_xs) { set_error("f32 vectors are off: call dasp_plan_set_f32_vectors(plan, 1) first"); return DASP_ERR_STATE; }
+    if (!dX || !dY) { set_error("null device pointer"); return DASP_ERR_ARG; }
+    const bool hub = p.lcb.n_rows() > 0;
+    if (hub && !p.dev->wide_part) { set_error("f32 vectors: the plan has no f64 hub partials"); return DASP_ERR_STATE; }
+    TpDev a = p.dev->tp;
+    a.xs = p.dev->wide_xs;
+    LcbDev q = p.dev->lcb;
+    q.partial = p.dev->wide_part; q.xpart = nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 hub_grid(q.n_rows);          // dasp_lcb_reduce_f32_kernel: one workgroup per hub row
+    if (hub) hipLaunchKernelGGL(dasp_lcb_f32_kernel, dim3(q.n_units), dim3(1024), lcb_lds_bytes<float>(q), s, q, dX);
+    if (a.n_units > 0) hipLaunchKernelGGL((dasp_tp_expand_kernel<float>), dim3(a.n_units), dim3(512), (size_t)a.cb * 4, s, a, dX);
+    if (a.n_rb > 0) hipLaunchKernelGGL(dasp_tp_reduce_f32_kernel, dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 8, s, a, dY, accumulate ? 1 : 0);
+    if (hub) hipLaunchKernelGGL(dasp_lcb_reduce_f32_kernel, hub_grid, dim3(256), kWavesPerWG * sizeof(double), s, q, dY);
+    HIP_TRY(hipGetLastError());
+    return DASP_OK;
 }
 
 }  // namespace dasp

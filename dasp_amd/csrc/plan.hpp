@@ -342,6 +342,9 @@ struct Plan {
     // the hub rows of an f16 two-phase hybrid (lcb above) sum exactly too (dasp_lcb_exact_kernel / dasp_lcb_reduce_exact_kernel, tp_exact.hpp): a launch-time switch over the
     // same lcb arrays (dasp_plan_set_hub_exact), independent of tp_exact; never set on any other plan, never stored in a plan file
     bool hub_exact = false;
+    // f32 vectors (dasp_plan_set_f32_vectors): the uploaded two-phase plan owns the wide xs stream (and the f64 hub partials) that dasp_plan_spmv_f32 needs
+    // (DevicePlan::wide_xs / wide_part); launch-time state of the device copy, false again after a re-upload, never stored in a plan file
+    bool f32_vectors = false;
 
     // value map (opt.value_map = 1): for every stored slot of a value array, 1 + the index of the nonzero of the CALLER's CSR it holds (through
     // the column sort and the panel split), 0 for a pad.  Same element counts as the value arrays; every nonzero appears exactly once over all

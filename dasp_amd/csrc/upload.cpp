@@ -33,6 +33,8 @@ Plan::~Plan()
         value_map_free(dev);
         if (dev->arena) (void)hipFree(dev->arena);
         if (dev->lcb_xpart) (void)hipFree(dev->lcb_xpart);
+        if (dev->wide_xs) (void)hipFree(dev->wide_xs);
+        if (dev->wide_part) (void)hipFree(dev->wide_part);
         if (dev->dargs) (void)hipFree(dev->dargs);
         std::free(dev->args_sent);
         delete dev;
@@ -163,7 +165,54 @@ static bool shared_ids_rule(const Plan &p, const SharedIds &s)
 
 void release_device(Plan &p)
 {
-    if (p.dev) { value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->lcb_xpart) (void)hipFree(p.dev->lcb_xpart); if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr; }
+    if (p.dev) {
+        value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->lcb_xpart) (void)hipFree(p.dev->lcb_xpart);
+        if (p.dev->wide_xs) (void)hipFree(p.dev->wide_xs);
+        if (p.dev->wide_part) (void)hipFree(p.dev->wide_part);
+        if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr;
+    }
+    p.f32_vectors = false;      // (the mode lives with the device copy: dasp_plan_set_f32_vectors)
+}
+
+// f32 vectors on / off for an uploaded f16 two-phase plan (dasp_plan_set_f32_vectors, which has checked the plan): the wide xs stream and, for a hybrid, the f64 hub
+// partials, zero-filled.  A failed allocation leaves the plan as it was.  Allocates / frees: never inside a stream capture; synchronises the device before freeing
+int set_f32_vectors_device(Plan &p, int on)
+{
+    DevicePlan *d = p.dev;
+    if (!d || !d->arena) { set_error("plan not uploaded"); return DASP_ERR_STATE; }
+    if (!on) {
+        if (!p.f32_vectors) return DASP_OK;
+        HIP_TRY(hipDeviceSynchronize());      // products still in flight read and write the two buffers
+        p.f32_vectors = false;
+        if (d->wide_xs) (void)hipFree(d->wide_xs);
+        if (d->wide_part) (void)hipFree(d->wide_part);
+        d->wide_xs = d->wide_part = nullptr;
+        return DASP_OK;
+    }
+    if (p.f32_vectors) return DASP_OK;
+    const size_t xs_bytes = std::max<size_t>(p.tp.segments * (size_t)kTpSeg * 4, 16);
+    const size_t part_bytes = p.lcb.n_rows() > 0 ? std::max<size_t>((size_t)p.lcb.n_cb * (size_t)p.lcb.n_rows() * 8, 16) : 0;
+    void *xs = nullptr, *part = nullptr;
+    auto make = [&]() -> hipError_t {
+        if (hipError_t e = hipMalloc(&xs, xs_bytes)) return e;
+        if (hipError_t e = hipMemset(xs, 0, xs_bytes)) return e;
+        if (part_bytes) {
+            if (hipError_t e = hipMalloc(&part, part_bytes)) return e;
+            if (hipError_t e = hipMemset(part, 0, part_bytes)) return e;
+        }
+        return hipDeviceSynchronize();          // the zeros are there before a product on any stream
+    };
+    if (hipError_t e = make()) {
+        if (xs) (void)hipFree(xs);
+        if (part) (void)hipFree(part);
+        (void)hipGetLastError();                // (not left behind for the next launch check)
+        set_error(std::string("dasp_plan_set_f32_vectors: ") + hipGetErrorString(e));
+        return DASP_ERR_HIP;
+    }
+    if (int rc = tp_kernels_allow_lds()) { (void)hipFree(xs); if (part) (void)hipFree(part); return rc; }
+    d->wide_xs = xs; d->wide_part = part;
+    p.f32_vectors = true;
+    return DASP_OK;
 }
 
 int upload_plan(Plan &p);

@@ -228,7 +228,8 @@ typedef struct dasp_options {
      * to run -- but are NOT covered by "exact"; dasp_plan_set_hub_exact (below) is the switch that makes them exact too.
      *   0 = off (default), 1 = a plan that comes out two-phase starts in exact mode; every other value is DASP_ERR_ARG.  Plans that are not two-phase ignore it
      *   (they are deterministic already).  Packed arrays, order_rid, the stats and every automatic choice are those of the same plan with 0; a plan file does not
-     *   store the mode (a loaded plan starts at 0).  DASP_ERR_ARG when a row of the streams holds >= 2^22 nonzeros (the 64-bit sums could overflow). */
+     *   store the mode (a loaded plan starts at 0).  DASP_ERR_ARG when a row of the streams holds >= 2^22 nonzeros (the 64-bit sums could overflow).
+     *   Governs the f16 entry points only: dasp_plan_spmv_f32 ignores it (an f16 x f32 product has no bounded fixed-point range). */
     int tp_exact;
 } dasp_options_t;
 
@@ -386,7 +387,8 @@ int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);
 
 /* exact phase 2 of a two-phase plan on (1) / off (0): dasp_options_t::tp_exact for a plan that exists -- host-built, device-built or loaded, uploaded or not;
  * needs no GPU; takes effect with the next launch (do not switch while a capture of this plan's launches is replayed: a captured graph keeps the kernel it
- * captured).  DASP_OK without effect on a plan that is not two-phase; DASP_ERR_ARG for another value, or when a row of the two-phase streams has >= 2^22 nonzeros. */
+ * captured).  DASP_OK without effect on a plan that is not two-phase; DASP_ERR_ARG for another value, or when a row of the two-phase streams has >= 2^22 nonzeros.
+ * Governs the f16 entry points only: dasp_plan_spmv_f32 ignores it. */
 int dasp_plan_set_tp_exact(dasp_plan_t *plan, int on);
 /* 1 for a two-phase plan in exact mode, else 0 */
 int dasp_plan_tp_exact(const dasp_plan_t *plan);
@@ -400,7 +402,8 @@ int dasp_plan_tp_exact(const dasp_plan_t *plan);
  * is replayed: a captured graph keeps the kernel it captured).  A plan file does not store the mode (a loaded plan starts at 0).  Costs 20 bytes per (hub row, column
  * block) in a device allocation of its own, made at upload whether the mode is on or not.
  * DASP_OK without effect on every other plan -- f64 plans, plans that are not two-phase, two-phase plans without hub rows, and column-panel plans (their panels are not
- * exact, so exact hub rows would promise nothing there); DASP_ERR_ARG for another value, or when a hub row holds >= 2^22 nonzeros (the 64-bit sums could overflow). */
+ * exact, so exact hub rows would promise nothing there); DASP_ERR_ARG for another value, or when a hub row holds >= 2^22 nonzeros (the 64-bit sums could overflow).
+ * Governs the f16 entry points only: dasp_plan_spmv_f32 ignores it (an f16 x f32 product has no bounded fixed-point range). */
 int dasp_plan_set_hub_exact(dasp_plan_t *plan, int on);
 /* 1 for a two-phase plan with hub rows whose hub kernels are the exact ones, else 0 */
 int dasp_plan_hub_exact(const dasp_plan_t *plan);
@@ -419,6 +422,37 @@ int dasp_plan_spmv(dasp_plan_t *plan, const void *dX, void *dY, void *stream);
  * read-modify-write (deterministic; f16: old y widened to f32, added, rounded once).  Lets a matrix split by columns
  * into several plans (dasp_mg_spmv: own / other ranks' columns) produce one y without a separate add. */
 int dasp_plan_spmv_acc(dasp_plan_t *plan, const void *dX, void *dY, void *stream);
+
+/* f32 vectors over an f16 two-phase plan: y = A*x with the matrix in binary16 and x, y in float (no reference counterpart).  The packed streams do not depend on the vector
+ * type (values f16, local rows and columns u16); only the xs stream between the two phases and the x / y accesses do, so the same plan serves both vector types: a PageRank
+ * vector with entries near 1e-7, or row sums beyond 65504, need no f64 plan (12 instead of 6 bytes per nonzero, and no two-phase form).  Streamed per stored element:
+ * 14 bytes (value 2, local row 2, local column 2, xs written and read 4 + 4) against the 10 of the f16 product.
+ * DEFINED RESULT, for every row: p_j = (double)a_j * (double)x_j, each product exact (an 11-bit times a 24-bit significand, exponents far inside f64); d = the f64 sum
+ * of the p_j; dasp_plan_spmv_f32 stores y = (float)d (an empty row: +0), dasp_plan_spmv_acc_f32 stores y = (float)((double)y_old + d).  Non-finite values follow IEEE
+ * through that arithmetic; pad elements never contribute.  Rows in the streams add through relaxed f64 LDS atomics, like the default phase 2: the order of addition is not
+ * fixed, and the result can differ from run to run only where (float)d sits on a rounding tie of the ~2^-53 reordering error.  Hub rows (a hybrid's column-blocked long
+ * rows) add in a fixed order.  dasp_plan_set_tp_exact and dasp_plan_set_hub_exact govern the f16 entry points only; the f32 ones ignore both.
+ *
+ * dasp_plan_set_f32_vectors(plan, 1) allocates what the f32 entry points need, 0 frees it.  Checked in this order:
+ *   DASP_ERR_ARG    NULL plan, `on` not 0 or 1, or a borrowed panel handle;
+ *   DASP_ERR_ARG    the plan is not an f16 two-phase plan (dasp_stats_t::two_phase != 1) -- dasp_options_t::two_phase = 1 forces that form for any f16 matrix without a
+ *                   column remap;
+ *   DASP_ERR_ARG    tp_col_block > 40960: the f32 slice of x of one column block (tp_col_block * 4 bytes) must fit the 160 KiB of LDS of one CU;
+ *   DASP_ERR_STATE  the plan is not uploaded;
+ *   a HIP error     an allocation failed: the plan is unchanged.
+ * Idempotent.  1 makes two device allocations of their own, zero-filled -- a wide xs of tp_segments * tp_seg_elems * 4 bytes and, for a hybrid, f64 partial sums of
+ * (column blocks) * lcb_rows * 8 bytes for the hub rows; the plan's arena stays byte for byte what it is.  It allocates (and synchronises the device, also before it
+ * frees): never call it inside a stream capture.  dasp_plan_destroy and a re-upload free both; the mode is launch-time state of the uploaded plan and is not stored in a
+ * plan file (a loaded or re-uploaded plan starts at 0). */
+int dasp_plan_set_f32_vectors(dasp_plan_t *plan, int on);
+/* 1 for a two-phase plan whose f32 entry points are ready, else 0 */
+int dasp_plan_f32_vectors(const dasp_plan_t *plan);
+/* y = A*x / y += A*x with f32 vectors: dX holds dasp_plan_x_len floats, dY rowA floats in the plan's y_order, both device pointers.  Asynchronous on `stream`, kernel
+ * launches only (hub stream kernel, phase 1, phase 2, hub reduce).  DASP_ERR_STATE unless dasp_plan_set_f32_vectors(plan, 1) has succeeded, DASP_ERR_ARG for null
+ * pointers.  The "one product in flight per plan" rule of dasp_plan_spmv holds, and f16 and f32 products of one plan must not overlap either (they share the hub rows'
+ * tables); they may alternate freely.  dasp_plan_update_values reaches these products too: they read the same packed values. */
+int dasp_plan_spmv_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream);
+int dasp_plan_spmv_acc_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream);
 
 /* the reference's timing protocol (dasp_f64.h:1285-1320,1394): `warmup` untimed + `iters`
  * timed back-to-back SpMVs on `stream`, one sync at the end.
