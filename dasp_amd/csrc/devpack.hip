@@ -1087,6 +1087,142 @@ int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val)
     if (val) HIP_TRYP(hipMemcpy(val, d.val, (size_t)p.nnz * (size_t)p.geo.vbytes, hipMemcpyDeviceToHost));
     return DASP_OK;
 }
+// ---- the densest span of every listed window (plan.cpp hybrid_windows; r12).  For a window, C = the remapped columns of all its nonzeros, duplicates included; a
+// candidate start is s = (c / A) * A for a c of C, count(s) = the entries of C in [s, s + cap_cols); the answer is the largest count and the SMALLEST s that reaches
+// it -- what both host searches compute.  Here: one key per nonzero of the listed windows, key = (index of the window in the list) << cbits | column, one radix sort
+// of all keys (hipcub), and every sorted element that opens its aligned group inside its window finds the end of [s, s + cap_cols) by a binary search in its window's
+// segment; a 64-bit maximum of count << 32 | (2^32 - 1 - s) per window takes the largest count and, among equals, the smallest start.  Integers and one commutative
+// maximum: nothing depends on the run.  The keys are 32 bits wide where the window index and the column fit them together (the 64-window sample of a matrix of up to
+// 2^26 columns), 64 bits otherwise; the scratch is two key buffers (the sort's double buffer) = 8 or 16 bytes per nonzero of the listed windows, 8 bytes per listed row,
+// and the sort's histograms.  It is gone when the function returns, before any packer allocates.
+namespace {
+
+constexpr int kSpanElems = 8;            // consecutive elements per thread of k_span_keys, as kFormElems
+
+// element e of the listed rows (start[i] = elements before listed row i, start[n_rows] = n; every listed window but the last holds R rows): its key
+template <class K>
+__global__ void k_span_keys(const int *start, const int *rows, int n_rows, int R, const int *rp, const int *ci, RemapDev remap, int cbits, long long n, K *keys)
+{
+    const long long e0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * kSpanElems;
+    if (e0 >= n) return;
+    int i = last_start_le(start, n_rows, e0), i_end = start[i + 1], j0 = rp[rows[i]] - start[i];
+    for (long long e = e0; e < min(n, e0 + kSpanElems); ++e) {
+        while (e >= i_end) { ++i; i_end = start[i + 1]; j0 = rp[rows[i]] - start[i]; }          // (e < n = start[n_rows]: i stays below n_rows)
+        keys[e] = ((K)(i / R) << cbits) | (K)remap(ci[j0 + (int)e]);
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1) { const unsigned long long u = __shfl_xor(v, o); v = u > v ? u : v; }
+    return v;
+}
+
+// sorted keys; seg[wi] = first sorted position of listed window wi (seg[n_list] = n).  One element per lane: the element that opens its aligned group counts the
+// entries of its window in [s, s + cap_cols).  A wave whose elements are all of one window (the usual case) sends one maximum, any other wave one per candidate
+template <class K>
+__global__ void k_span_best(const K *keys, const int *seg, int cbits, int A, int cap_cols, long long n, unsigned long long *best)
+{
+    const K cmask = (K)(((K)1 << cbits) - 1);
+    for (long long i0 = (long long)blockIdx.x * blockDim.x; i0 < n; i0 += (long long)gridDim.x * blockDim.x) {      // (i0 is uniform: the waves stay whole for the shuffles)
+        const long long i = i0 + threadIdx.x;
+        unsigned long long v = 0;
+        int wi = -1;
+        if (i < n) {
+            const K key = keys[i];
+            wi = (int)(key >> cbits);
+            const int s = ((int)(key & cmask) / A) * A;
+            bool opens = i == seg[wi];
+            if (!opens) opens = (int)(keys[i - 1] & cmask) < s;          // (i - 1 is of the same window)
+            if (opens) {
+                const long long lim = (long long)s + cap_cols;
+                long long lo = i, hi = seg[wi + 1];                      // keys[lo] < lim <= keys[hi] (hi: the segment's end)
+                while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if ((long long)(keys[mid] & cmask) < lim) lo = mid; else hi = mid; }
+                v = ((unsigned long long)(hi - i) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)s);
+            }
+        }
+        const int w_lo = wave_min(wi < 0 ? 2147483647 : wi), w_hi = wave_max(wi);
+        if (w_hi < 0) continue;
+        if (w_lo == w_hi) {
+            v = wave_max_u64(v);
+            if ((threadIdx.x & 63) == 0 && v) atomicMax(best + w_hi, v);
+        } else if (v) atomicMax(best + wi, v);
+    }
+}
+
+inline int bits_for(long long count) { int b = 1; while (b < 62 && (count - 1) >> b) ++b; return b; }      // bits that hold 0 .. count - 1 (at least one)
+
+template <class K>
+int densest_spans_typed(const Plan &p, const DevCsr &d, const std::vector<int> &rows, const std::vector<int> &start, const std::vector<int> &seg, int R,
+                        int cbits, int wbits, int cap_cols, int A, std::vector<unsigned long long> &best)
+{
+    const long long n = start.back();
+    const size_t n_rows = rows.size(), n_list = best.size();
+    FormScratch sc;
+    auto *d_rows = static_cast<int *>(sc.get(n_rows * 4)), *d_start = static_cast<int *>(sc.get((n_rows + 1) * 4)), *d_seg = static_cast<int *>(sc.get((n_list + 1) * 4));
+    auto *d_best = static_cast<unsigned long long *>(sc.get(n_list * 8));
+    auto *k0 = static_cast<K *>(sc.get((size_t)n * sizeof(K))), *k1 = static_cast<K *>(sc.get((size_t)n * sizeof(K)));
+    if (!d_rows || !d_start || !d_seg || !d_best || !k0 || !k1) return kDevNoScratch;
+    hipcub::DoubleBuffer<K> kb(k0, k1);
+    size_t tmp_bytes = 0;
+    if (hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, kb, (int)n, 0, cbits + wbits) != hipSuccess) { set_error("hipcub radix sort (densest spans)"); return DASP_ERR_HIP; }
+    void *tmp = sc.get(tmp_bytes);
+    if (!tmp) return kDevNoScratch;
+    if (std::getenv("DASP_VERBOSE"))
+        std::fprintf(stderr, "[dasp hybrid] %zu windows, %lld nonzeros, %d-bit keys: scratch %.2f bytes per nonzero\n", n_list, n, (int)sizeof(K) * 8,
+                     (double)(2 * (size_t)n * sizeof(K) + tmp_bytes + n_rows * 8 + n_list * 12 + 8) / (double)n);
+    RemapHolder rm; if (int rc = rm.init(p)) return rc;
+    HIP_TRYP(hipMemcpy(d_rows, rows.data(), n_rows * 4, hipMemcpyHostToDevice));
+    HIP_TRYP(hipMemcpy(d_start, start.data(), (n_rows + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRYP(hipMemcpy(d_seg, seg.data(), (n_list + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRYP(hipMemset(d_best, 0, n_list * 8));
+    hipLaunchKernelGGL((k_span_keys<K>), dim3(grid_for(n, kSpanElems)), dim3(256), 0, 0, d_start, d_rows, (int)n_rows, R, d.rp, d.ci, rm.r, cbits, n, k0);
+    HIP_TRYP(hipGetLastError());
+    if (hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, kb, (int)n, 0, cbits + wbits) != hipSuccess) { set_error("hipcub radix sort (densest spans)"); return DASP_ERR_HIP; }
+    hipLaunchKernelGGL((k_span_best<K>), dim3(std::min(grid_for(n), 4096u)), dim3(256), 0, 0, kb.Current(), d_seg, cbits, A, cap_cols, n, d_best);
+    HIP_TRYP(hipGetLastError());
+    HIP_TRYP(hipMemcpy(best.data(), d_best, n_list * 8, hipMemcpyDeviceToHost));
+    return DASP_OK;
+}
+
+}  // namespace
+
+// hmin[w], hin[w] for every w of wlist (ascending, so that only its last window can hold fewer than R rows); the others are left alone.  kDevNoScratch: the scratch
+// did not fit, or DASP_DEVPACK_HYBRID (read at every call) says so -- "noscratch" is the test hook of the fallback, "0" the A/B knob -- and the caller fetches the ids
+int devpack_densest_spans(const Plan &p, const DevCsr &d, const raw_vector<int> &ridW, const raw_vector<int> &lenW, int R, const std::vector<int> &wlist,
+                          long long cap_cols, int A, int *hmin, long long *hin)
+{
+    const char *const knob = std::getenv("DASP_DEVPACK_HYBRID");
+    if (knob && (std::strcmp(knob, "noscratch") == 0 || std::strcmp(knob, "0") == 0)) return kDevNoScratch;
+    const bool keys64 = knob && std::strcmp(knob, "keys64") == 0;          // test hook: the 64-bit keys where 32 would do (else they need 2^26 columns or thousands of windows)
+    const int nmed = (int)ridW.size(), n_list = (int)wlist.size();
+    std::vector<int> rows, start, seg((size_t)n_list + 1, 0);
+    long long n = 0;
+    for (int wi = 0; wi < n_list; ++wi) {
+        const int a0 = wlist[(size_t)wi] * R, a1 = std::min(nmed, a0 + R);
+        if (wi + 1 < n_list && a1 - a0 != R) return kDevNoScratch;          // (a short window in the middle of the list: the kernels take listed row i for window i / R)
+        seg[(size_t)wi] = (int)n;
+        for (int i = a0; i < a1; ++i) { rows.push_back(ridW[(size_t)i]); start.push_back((int)n); n += lenW[(size_t)i]; }
+        hmin[wlist[(size_t)wi]] = 0; hin[wlist[(size_t)wi]] = 0;
+    }
+    start.push_back((int)n); seg[(size_t)n_list] = (int)n;
+    if (n <= 0) return DASP_OK;
+    const long long xl = p.opt.n_parts > 0 ? (long long)p.opt.n_parts * p.opt.part_stride : (long long)p.n;
+    const int cbits = bits_for(std::max<long long>(xl, 2)), wbits = bits_for(std::max(n_list, 2));
+    if (cbits > 31 || n >= (1ll << 31)) return kDevNoScratch;
+    std::vector<unsigned long long> best((size_t)n_list, 0);
+    const int rc = cbits + wbits <= 32 && !keys64 ? densest_spans_typed<unsigned>(p, d, rows, start, seg, R, cbits, wbits, (int)cap_cols, A, best)
+                                       : densest_spans_typed<unsigned long long>(p, d, rows, start, seg, R, cbits, wbits, (int)cap_cols, A, best);
+    if (rc != DASP_OK) return rc;
+    for (int wi = 0; wi < n_list; ++wi) {
+        const unsigned long long v = best[(size_t)wi];
+        if (!v) continue;                                                   // an empty window: (0, 0)
+        hin[wlist[(size_t)wi]] = (long long)(v >> 32);
+        hmin[wlist[(size_t)wi]] = (int)(0xFFFFFFFFu - (unsigned)(v & 0xFFFFFFFFu));
+    }
+    return DASP_OK;
+}
+
 int devpack_current_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; } return d; }
 void devpack_use_device(int device) { if (device >= 0) (void)hipSetDevice(device); }
 

@@ -269,6 +269,74 @@ struct CsrProbe {
         });
         return DASP_OK;
     }
+    // the densest span of cap_cols columns of the windows wlist[] (ascending; window w = rows ridW[w * R .. min(n, (w + 1) * R)), their lengths in lenW): hin[w] =
+    // the most entries of the window inside [s, s + cap_cols) over the starts s aligned to A, hmin[w] = the first s that reaches it; an empty window gives (0, 0).
+    // A device CSR whose search finds no room for its scratch (kDevNoScratch) has its column ids fetched ONCE into `fetched` (the caller keeps it between its
+    // calls and adds *fetch_bytes to Plan::csr_fetch_bytes) and is searched on the host like a host CSR
+    int densest_spans(const raw_vector<int> &ridW, const raw_vector<int> &lenW, int n, int R, const std::vector<int> &wlist, long long cap_cols, int A,
+                      int *hmin, long long *hin, raw_vector<int> &fetched, long long *fetch_bytes) const
+    {
+        const int *ci = this->ci;
+        if (dev) {
+            if (fetched.empty()) {
+                const int rc = devpack_densest_spans(p, *dev, ridW, lenW, R, wlist, cap_cols, A, hmin, hin);
+                if (rc != kDevNoScratch) return rc;
+                fetched.resize((size_t)p.nnz);
+                if (int rc2 = devpack_fetch_csr(p, *dev, fetched.data(), nullptr)) return rc2;
+                *fetch_bytes += (long long)p.nnz * 4;
+            }
+            ci = fetched.data();
+        }
+        const int *const rp = this->rp;
+        const Remap remap = this->remap;
+        const int mfma_rows = n;
+        const bool force_sort = std::getenv("DASP_HYBRID_SORT") != nullptr;       // test knob: the sort-based search (tests compare the two)
+        parallel_for((long long)wlist.size(), threads, 4, [&](long long w0, long long w1) {
+            std::vector<int> cols, hist;
+            for (long long wi = w0; wi < w1; ++wi) {
+                const int w = wlist[(size_t)wi];
+                const int a0 = (int)w * R, a1 = std::min(mfma_rows, a0 + R);
+                cols.clear();
+                int cmin_w = 2147483647, cmax_w = -1;
+                for (int i = a0; i < a1; ++i) {
+                    const int r = ridW[i];
+                    for (int j = rp[r]; j < rp[r + 1]; ++j) { const int c = remap(ci[j]); cols.push_back(c); cmin_w = std::min(cmin_w, c); cmax_w = std::max(cmax_w, c); }
+                }
+                // best 16-byte-aligned start: for every aligned start that holds an entry, the entries in [start, start + cap_cols); the
+                // first start with the largest count wins.  (An entry c that is not the smallest of its aligned group counts fewer entries
+                // than the group's smallest one -- which is itself inside [group start, c) -- so only group starts compete.)
+                long long best = 0; int bs = 0;
+                const long long g0 = cols.empty() ? 0 : cmin_w / A, ngrp = cols.empty() ? 0 : cmax_w / A - g0 + 1;
+                if (!cols.empty() && ngrp <= 4 * (long long)cols.size() + 1024 && !force_sort) {
+                    // dense enough: a histogram over the aligned groups and a sliding sum -- O(entries + groups) instead of a sort
+                    hist.assign((size_t)ngrp + 1, 0);
+                    for (int c : cols) hist[(size_t)(c / A - g0)]++;
+                    const long long wg = cap_cols / A;                                  // groups per span
+                    long long run = 0;
+                    for (long long g = 0; g < std::min(wg, ngrp); ++g) run += hist[(size_t)g];
+                    for (long long g = 0; g < ngrp; ++g) {
+                        if (hist[(size_t)g] > 0 && run > best) { best = run; bs = (int)((g0 + g) * A); }
+                        run -= hist[(size_t)g];
+                        if (g + wg < ngrp) run += hist[(size_t)(g + wg)];
+                    }
+                } else {
+                std::sort(cols.begin(), cols.end());
+                size_t hi_i = 0;
+                for (size_t lo_i = 0; lo_i < cols.size(); ++lo_i) {
+                    if (lo_i && cols[lo_i] == cols[lo_i - 1]) continue;
+                    const long long st = (cols[lo_i] / A) * A;
+                    if (hi_i < lo_i) hi_i = lo_i;
+                    while (hi_i < cols.size() && cols[hi_i] < st + cap_cols) ++hi_i;
+                    // entries between the aligned start and cols[lo_i] belong to the span too, but they are < A away: ignore them
+                    const long long cnt = (long long)(hi_i - lo_i);
+                    if (cnt > best) { best = cnt; bs = (int)st; }
+                }
+                }
+                hmin[w] = bs; hin[w] = best;
+            }
+        });
+        return DASP_OK;
+    }
     // gathered columns: the (remapped) ids of the first `cap` nonzeros of every row of `rows`, one row after the other
     int columns_of_rows(const std::vector<int> &rows, int cap, std::vector<int> &out) const
     {
@@ -978,38 +1046,37 @@ template <class T> static void fit_windows(Build<T> &bld, Windows &w)
 
 // ---- hybrid windows: when the whole span of a window does not fit (graph-like rows: most columns near the rows -- the
 // pages of a host, the members of a community -- plus a scattered remainder), stage the DENSEST span of cap bytes and let
-// the gathers that fall outside it read global memory (kernel: XHyb).  Host CSR only.  It pays on rows of even length whose
+// the gathers that fall outside it read global memory (kernel: XHyb).  The search is CsrProbe::densest_spans: its own loops on a host CSR, a sort on
+// the GPU for a device CSR (devpack_densest_spans), with the same answer.  It pays on rows of even length whose
 // columns form a band plus outliers (tools/hybrid_probe.py: 2 M rows of 14, +-3000 band + 10 % anywhere, f64 0.234 -> 0.189 ms,
 // f16 0.086 -> 0.061 ms; +-8000 + 3 %: 0.190 -> 0.126 ms); on the power-law stand-ins the window workgroups themselves cost
 // more than the LDS gathers save (webbase-1M 14.6 -> 22.4 us with 85 % of the medium gathers staged, ljournal-2008
 // 0.545 -> 0.587 ms with 53 %: one 1024-thread workgroup per window balances rows of 5..255 nonzeros badly).  So auto
 // asks for even rows (longest <= 4 x the mean) on top of: strict windows cover < half, densest spans cover >= 60 %.
-template <class T> static void hybrid_windows(Build<T> &bld, Windows &w)
+template <class T> static int hybrid_windows(Build<T> &bld, Windows &w)
 {
     Plan &p = bld.p;
     const Geometry &geo = bld.geo;
-    const int *rp = bld.rp, *ci = bld.ci;
-    const DevCsr *dev = bld.dev;
-    const Remap remap = bld.remap;
-    const int threads = bld.threads, mfma_rows = bld.mfma_rows, R = w.R, nW = w.nW, A = w.A;
+    const int mfma_rows = bld.mfma_rows, R = w.R, nW = w.nW, A = w.A;
     const bool order_only = w.order_only;
-    const raw_vector<int> &lenM = bld.lenM, &ridW = w.ridW;
+    const raw_vector<int> &lenM = bld.lenM, &ridW = w.ridW, &lenW = w.lenW;
     const std::vector<long long> &wnnz = w.wnnz;
     std::vector<int> &cmin = w.cmin, &wlen = w.wlen;
     const long long all = w.all;
     long long &fit = w.fit;
     int &maxlen = w.maxlen;
     double &window_frac = bld.window_frac;
+    const CsrProbe probe = bld.probe();
     p.win_hybrid = false;
     const bool even_rows = mfma_rows > 0 && (long long)lenM[0] * mfma_rows <= 4 * std::max<long long>(1, all);
-    if (!dev && !order_only && p.opt.x_window_hybrid >= 0 &&
+    if (!order_only && p.opt.x_window_hybrid >= 0 &&
         (p.opt.x_window_hybrid > 0 || (p.opt.x_window == 0 && window_frac < 0.5 && even_rows))) {
         const int hcap = p.opt.x_window > 0 ? std::min(p.opt.x_window, kWinLdsMax) : 80 * 1024;    // two workgroups per CU
         const long long cap_cols = std::max<long long>(A, (hcap / geo.vbytes / A) * A);
         const long long xl = p.opt.n_parts > 0 ? (long long)p.opt.n_parts * p.opt.part_stride : (long long)p.n;
         std::vector<int> hmin(nW), hlen(nW);
         std::vector<long long> hin(nW);
-        const bool force_sort = std::getenv("DASP_HYBRID_SORT") != nullptr;       // test knob: the sort-based search (tests compare the two)
+        raw_vector<int> fetched;       // a device CSR whose search had no room for its scratch: its column ids, fetched once (CsrProbe::densest_spans)
         // auto mode on a large matrix: the densest spans of 64 evenly spaced windows first -- when they hold under 55 % of those
         // windows' gathers the whole will not reach 60 %, and sorting every window's columns is skipped (HV15R: 0.33 s of the host
         // path, its three-plane rows give 33 %; nlpkkt160: 0.45 s, ~50 %)
@@ -1018,51 +1085,8 @@ template <class T> static void hybrid_windows(Build<T> &bld, Windows &w)
         bool sampled = !wlist.empty();
         for (int pass = sampled ? 0 : 1; pass < 2; ++pass) {
         if (pass == 1) { wlist.resize((size_t)nW); for (int w = 0; w < nW; ++w) wlist[(size_t)w] = w; }
-        parallel_for((long long)wlist.size(), threads, 4, [&](long long w0, long long w1) {
-            std::vector<int> cols, hist;
-            for (long long wi = w0; wi < w1; ++wi) {
-                const int w = wlist[(size_t)wi];
-                const int a0 = (int)w * R, a1 = std::min(mfma_rows, a0 + R);
-                cols.clear();
-                int cmin_w = 2147483647, cmax_w = -1;
-                for (int i = a0; i < a1; ++i) {
-                    const int r = ridW[i];
-                    for (int j = rp[r]; j < rp[r + 1]; ++j) { const int c = remap(ci[j]); cols.push_back(c); cmin_w = std::min(cmin_w, c); cmax_w = std::max(cmax_w, c); }
-                }
-                // best 16-byte-aligned start: for every aligned start that holds an entry, the entries in [start, start + cap_cols); the
-                // first start with the largest count wins.  (An entry c that is not the smallest of its aligned group counts fewer entries
-                // than the group's smallest one -- which is itself inside [group start, c) -- so only group starts compete.)
-                long long best = 0; int bs = 0;
-                const long long g0 = cols.empty() ? 0 : cmin_w / A, ngrp = cols.empty() ? 0 : cmax_w / A - g0 + 1;
-                if (!cols.empty() && ngrp <= 4 * (long long)cols.size() + 1024 && !force_sort) {
-                    // dense enough: a histogram over the aligned groups and a sliding sum -- O(entries + groups) instead of a sort
-                    hist.assign((size_t)ngrp + 1, 0);
-                    for (int c : cols) hist[(size_t)(c / A - g0)]++;
-                    const long long wg = cap_cols / A;                                  // groups per span
-                    long long run = 0;
-                    for (long long g = 0; g < std::min(wg, ngrp); ++g) run += hist[(size_t)g];
-                    for (long long g = 0; g < ngrp; ++g) {
-                        if (hist[(size_t)g] > 0 && run > best) { best = run; bs = (int)((g0 + g) * A); }
-                        run -= hist[(size_t)g];
-                        if (g + wg < ngrp) run += hist[(size_t)(g + wg)];
-                    }
-                } else {
-                std::sort(cols.begin(), cols.end());
-                size_t hi_i = 0;
-                for (size_t lo_i = 0; lo_i < cols.size(); ++lo_i) {
-                    if (lo_i && cols[lo_i] == cols[lo_i - 1]) continue;
-                    const long long st = (cols[lo_i] / A) * A;
-                    if (hi_i < lo_i) hi_i = lo_i;
-                    while (hi_i < cols.size() && cols[hi_i] < st + cap_cols) ++hi_i;
-                    // entries between the aligned start and cols[lo_i] belong to the span too, but they are < A away: ignore them
-                    const long long cnt = (long long)(hi_i - lo_i);
-                    if (cnt > best) { best = cnt; bs = (int)st; }
-                }
-                }
-                hmin[w] = bs; hin[w] = best;
-                hlen[w] = (int)std::min<long long>(cap_cols, xl - bs);
-            }
-        });
+        if (int rc = probe.densest_spans(ridW, lenW, mfma_rows, R, wlist, cap_cols, A, hmin.data(), hin.data(), fetched, &p.csr_fetch_bytes)) return rc;
+        for (int w : wlist) hlen[(size_t)w] = (int)std::min<long long>(cap_cols, xl - hmin[(size_t)w]);
         if (pass == 0) {
             long long in_s = 0, all_s = 0;
             for (int w : wlist) { in_s += hin[(size_t)w]; all_s += wnnz[(size_t)w]; }
@@ -1083,6 +1107,7 @@ template <class T> static void hybrid_windows(Build<T> &bld, Windows &w)
             window_frac = all > 0 ? (double)fit / (double)all : 0.0;
         }
     }
+    return DASP_OK;
 }
 
 // the automatic rule of decide_windows, asked once the windows cover half of the matrix: *pay = staging their x in LDS is worth its copy
@@ -1191,7 +1216,7 @@ template <class T> static int decide_windows(Build<T> &bld)
     // still beats global gathers on band-scattered rows (+-30 k columns, f16: 98.8 -> 65.9 us; +-8 k, f64: 166.8 -> 115.8 us)
     if (p.opt.x_window == 0 && bld.window_frac < 0.5) { w.cap_bytes = kWinLdsMax; fit_windows(bld, w); }
     const bool force = p.opt.x_window > 0;
-    hybrid_windows(bld, w);
+    if (int rc = hybrid_windows(bld, w)) return rc;
     bool worth = bld.window_frac >= 0.5 && (double)w.all >= 0.5 * (double)nnz;
     if (worth && !force && !w.order_only) { if (int rc = windows_pay(bld, &worth)) return rc; }
     const int R = w.R;

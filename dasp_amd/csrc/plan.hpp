@@ -404,6 +404,12 @@ int devpack_line_scatter(const Plan &p, const DevCsr &d, const std::vector<int> 
 int devpack_row_coherence(const Plan &p, const DevCsr &d, const std::vector<int> &rows, int within, long long *near, long long *entries);
 int devpack_chunk_spans(const Plan &p, const DevCsr &d, const raw_vector<int> &ridM, const raw_vector<int> &lenM,
                         const std::vector<int> &nchunks, int *k16, unsigned long long *narrow_mask);      // narrow_mask: nullptr or [blocks] (plan.cpp)
+// the densest span of cap_cols columns (starts aligned to A) of the windows wlist[] (ascending) over ridW / lenW, R rows each: hin[w] = the most nonzeros of window w
+// inside one span, hmin[w] = the smallest aligned start that reaches it, (0, 0) for an empty window.  DASP_OK, an error, or kDevNoScratch (below): no room for the
+// search's scratch, or DASP_DEVPACK_HYBRID = noscratch / 0 (read at every call) -- the caller fetches the column ids and searches on the host.
+// (DASP_DEVPACK_HYBRID = keys64, a test hook: the 64-bit keys of the large matrices where 32 bits would do)
+int devpack_densest_spans(const Plan &p, const DevCsr &d, const raw_vector<int> &ridW, const raw_vector<int> &lenW, int R, const std::vector<int> &wlist,
+                          long long cap_cols, int A, int *hmin, long long *hin);
 int devpack_all(Plan &p, const DevCsr &d, const PackMeta &m);
 int devpack_finish_panels(Plan &p);
 int devpack_fetch_csr(const Plan &p, const DevCsr &d, int *ci, void *val);      // column ids and values of a device CSR -> host arrays of nnz elements (val nullptr: the ids only); the caller counts them in Plan::csr_fetch_bytes

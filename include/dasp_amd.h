@@ -143,7 +143,8 @@ typedef struct dasp_options {
      * does not fit in LDS, the window's DENSEST span of `x_window` bytes (auto: 81920) is staged and the gathers that fall outside
      * it read global memory.  0 = auto: when the strict windows cover < half of the medium nonzeros, the densest spans would
      * cover >= 60 % and the rows are of even length (longest <= 4 x the mean: a band plus outliers; on power-law rows the window
-     * workgroups cost more than the LDS gathers save); -1 = never; 1 = force (with x_window >= 0).  Host CSR only. */
+     * workgroups cost more than the LDS gathers save); -1 = never; 1 = force (with x_window >= 0).  Host and device CSR alike:
+     * dasp_plan_create_device finds the densest spans with kernels and stages the same ones. */
     int x_window_hybrid;
     /* the longest medium rows as wave-sized pieces (stored and multiplied like the long rows: CSR order, one wave per piece of
      * <= long_piece nonzeros, all 64 lanes on one row) instead of 16-row blocks, whose ceil(len / K) MFMA steps run serially in one
@@ -289,13 +290,16 @@ int dasp_plan_create(dasp_plan_t **plan, int precision, int rowA, int colA, int 
 /* the same with the CSR already on the current HIP device (dRowPtr / dColIdx / dVal are device pointers): only the row
  * pointer visits the host; the nonzeros are range-checked, scanned, split into column panels where the plan uses them, and packed by
  * kernels.  The plan comes back uploaded and produces bit-identical packed arrays to dasp_plan_create, with the same
- * automatic choices (only hybrid x windows are decided on a host CSR alone).  That includes the two-phase streams and the column-blocked long
+ * automatic choices.  That includes hybrid x windows (x_window_hybrid: the densest span of every window is searched on the device, by a sort of the
+ * windows' column ids; its scratch -- 8 or 16 bytes per nonzero of the searched windows -- is freed before the packers allocate), the two-phase streams and the column-blocked long
  * rows (and the panels beside them): a stable radix sort on the device ranks every nonzero inside its tile / piece as the host packers' serial
  * walks do.  Such a plan therefore holds NO host copy of its nnz-sized streams, like every other device-built plan: dasp_plan_host_array of
  * tp_lcol / tp_lrow / tp_val / tp_dst / lcb_val / lcb_lcol answers DASP_ERR_STATE (dasp_plan_download_array reads them), dasp_plan_save refuses;
  * the small tables (tp_rb_row0, tp_rb_seg0, tp_unit, lcb_ptr, lcb_unit, lcb_row_id, lcb_row_dst, order) stay on the host.  The host packers remain
  * as the fallback of those two forms only -- when the device packers' scratch (about 24 bytes per nonzero while they run) cannot be allocated, or
- * DASP_DEVPACK_FORMS=0 is set (read at every call): the column ids and values are then copied to the host once; dasp_plan_csr_fetch_bytes tells. */
+ * DASP_DEVPACK_FORMS=0 is set (read at every call): the column ids and values are then copied to the host once; dasp_plan_csr_fetch_bytes tells.  The
+ * search of the hybrid windows has the same kind of fallback and a knob of its own: without room for its scratch, or under DASP_DEVPACK_HYBRID=0, the column ids
+ * alone (4 bytes per nonzero) are copied to the host once and searched there. */
 int dasp_plan_create_device(dasp_plan_t **plan, int precision, int rowA, int colA, int nnzA,
                             const int *dRowPtr, const int *dColIdx, const void *dVal, const dasp_options_t *opt);
 /* Placement trials (r3; opt-in since r4): the same packed bytes run the HBM-bound kernels at one of two speeds ~8 % apart depending on where the
