@@ -17,6 +17,7 @@ from . import _lib
 from ._lib import DaspError, Options, Stats
 
 Y_PERMUTED, Y_NATURAL = 0, 1
+MIN_PLUS, MIN_SECOND = 1, 2      # dasp_semiring (Plan.spmv_semiring_f32)
 
 
 def _vp(a):
@@ -347,6 +348,13 @@ class Plan:
         f = _lib.lib().dasp_plan_spmv_acc_f32 if accumulate else _lib.lib().dasp_plan_spmv_f32
         fp = C.POINTER(C.c_float)
         _lib.check(f(self._h, C.cast(C.c_void_p(dX), fp), C.cast(C.c_void_p(dY), fp), C.c_void_p(stream)))
+
+    def spmv_semiring_f32(self, semiring, dX, dY, stream=0, accumulate=False):
+        """y_i = min_j (a_ij + x_j) (MIN_PLUS) or min_j x_j (MIN_SECOND) over the stored entries of an f16 two-phase plan with float32 vectors
+        (dasp_plan_spmv_semiring_f32); accumulate: y_i = min(y_old_i, that), the Bellman-Ford relaxation.  dX, dY: integer device addresses of x_len / rowA float32
+        values, dX == dY allowed; needs set_f32_vectors(1).  An empty row gives +inf (keeps y_old when accumulating)."""
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.lib().dasp_plan_spmv_semiring_f32(self._h, int(semiring), C.cast(C.c_void_p(dX), fp), C.cast(C.c_void_p(dY), fp), int(accumulate), C.c_void_p(stream)))
 
     def time(self, dX, dY, stream=0, warmup=100, iters=1000):
         """The reference's protocol (dasp_f64.h:1285-1320): returns (wall_ms, event_ms) per SpMV."""

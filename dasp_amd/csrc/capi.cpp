@@ -451,6 +451,18 @@ static int spmv_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream,
 int dasp_plan_spmv_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream) { return spmv_f32(plan, dX, dY, stream, false); }
 int dasp_plan_spmv_acc_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream) { return spmv_f32(plan, dX, dY, stream, true); }
 
+// min-plus / min-second products over the arrays and the two buffers of the f32-vector mode; the checks come in the header's order
+int dasp_plan_spmv_semiring_f32(dasp_plan_t *plan, int semiring, const float *dX, float *dY, int accumulate, void *stream)
+{
+    if (!plan) { set_error("dasp_plan_spmv_semiring_f32: null plan"); return DASP_ERR_ARG; }
+    if (!dX || !dY) { set_error("dasp_plan_spmv_semiring_f32: null device pointer"); return DASP_ERR_ARG; }
+    if (semiring != DASP_MIN_PLUS && semiring != DASP_MIN_SECOND) { set_error("semiring must be DASP_MIN_PLUS (1) or DASP_MIN_SECOND (2)"); return DASP_ERR_ARG; }
+    if (accumulate != 0 && accumulate != 1) { set_error("accumulate must be 0 or 1"); return DASP_ERR_ARG; }
+    if (plan->impl.panel) { set_error("dasp_plan_spmv_semiring_f32: a borrowed panel handle"); return DASP_ERR_ARG; }
+    if (!plan->impl.f32_vectors) { set_error("f32 vectors are off: call dasp_plan_set_f32_vectors(plan, 1) on the uploaded two-phase plan first"); return DASP_ERR_STATE; }
+    return launch_spmv_semiring_f32(plan->impl, semiring, dX, dY, stream, accumulate != 0);
+}
+
 int dasp_plan_spmv(dasp_plan_t *plan, const void *dX, void *dY, void *stream)
 {
     if (!plan) return DASP_ERR_ARG;

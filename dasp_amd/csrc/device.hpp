@@ -152,6 +152,8 @@ int upload_plan_unpacked(Plan &p);     // for the device packers: arena + O(rows
 // kernels.hip: one SpMV of an uploaded plan (asynchronous); what upload.cpp asks the kernels
 int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate);
 int launch_spmv_f32(Plan &p, const float *dX, float *dY, void *stream, bool accumulate);      // kernels.hip: the same with f32 vectors (an f16 two-phase plan in f32-vector mode)
+// kernels.hip: y = (min(y_old,)) min_j (a_ij + x_j) / min_j x_j over the same arrays and the two buffers of the f32-vector mode (dasp_plan_spmv_semiring_f32)
+int launch_spmv_semiring_f32(Plan &p, int semiring, const float *dX, float *dY, void *stream, bool accumulate);
 int set_f32_vectors_device(Plan &p, int on);    // upload.cpp: makes / frees DevicePlan::wide_xs and wide_part of an uploaded two-phase plan and sets Plan::f32_vectors
 int spmv_kernel_allow_full_lds(int precision, bool c16);
 int tp_kernels_allow_lds();             // kernels.hip: the two-phase kernels, the f32-vector ones included, may use up to 160 KiB of dynamic LDS (called at upload)

@@ -765,6 +765,165 @@ __global__ __launch_bounds__(256) void dasp_lcb_reduce_f32_kernel(LcbDev a, floa
     if (threadIdx.x == 0) { const int d = a.row_dst[i]; y[d] = (float)((double)y[d] + ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]))); }
 }
 
+// ------------------------------------------------------------------ min-plus / min-second products with f32 vectors (dasp_plan_spmv_semiring_f32)
+// y_i = min_j (a_ij + x_j)  (PLUS)  or  min_j x_j  (the pattern only) over the same packed arrays, the wide xs and the hub partial buffer of the f32-vector mode.
+// Phase 1 is dasp_tp_expand_kernel<float> as it is; the kernels below are phase 2 and the hub rows.  Every minimum is taken on the ORDER-PRESERVING INTEGER IMAGE of
+// an f32 (tp_min_key: unsigned compare == float compare, -0 below +0, +NaN above +inf, -NaN below -inf): a total order, so the result -- bits included -- depends on
+// neither the order in which the LDS atomics land nor the block geometry.  A STORED zero is a candidate like any other (an edge of length 0); pads are known by
+// lrow == kTpPadRow / lcol == kLcbPadCol, never by their value.
+constexpr unsigned kMinKeyInf = 0xFF800000u;          // tp_min_key(+inf): the identity
+__device__ __forceinline__ unsigned tp_min_key(float f) { const unsigned b = __float_as_uint(f); return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+__device__ __forceinline__ float tp_min_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_mov_u32(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false); }
+
+// Phase 2: the grid, the three streams and the loads of dasp_tp_reduce_f32_kernel (PLUS = false: val is not loaded); an output position is ONE 32-bit word in LDS
+// (rb_max x 4 bytes dynamic).  Both collision savers stay -- the in-lane run of equal lrow is a min in a register, the segmented DPP scan a min on one dword -- and the
+// run's last lane issues one no-return ds_min_u32.
+template <bool PLUS>
+__global__ __launch_bounds__(512) void dasp_tp_reduce_min_f32_kernel(TpDev a, float *__restrict__ y, int acc)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    typedef _Float16 vec8 __attribute__((ext_vector_type(8)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    unsigned *yl = reinterpret_cast<unsigned *>(lds_raw);
+    const int r = blockIdx.x;
+    const int p0 = a.rb_row0[r], rows = a.rb_row0[r + 1] - p0;
+    for (int i = threadIdx.x; i < rows; i += 512) yl[i] = kMinKeyInf;
+    __syncthreads();
+    const int s0 = a.rb_seg0[r], s1 = a.rb_seg0[r + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int LPS = kTpSeg / 8, SPW = 64 / LPS;
+    const int sub = lane / LPS, off = (lane % LPS) * 8;
+    const _Float16 *val = static_cast<const _Float16 *>(a.val);
+    const float *xs = static_cast<const float *>(a.xs);
+#pragma unroll 2
+    for (int g = s0 + wave * SPW; g < s1; g += 8 * SPW) {
+        const int seg = g + sub;
+        if (seg < s1) {
+            const size_t at = (size_t)seg * kTpSeg + off;
+            vec8 v = {};
+            if constexpr (PLUS) v = __builtin_nontemporal_load(reinterpret_cast<const vec8 *>(val + at));
+            const tp_u16x8 lr = __builtin_nontemporal_load(reinterpret_cast<const tp_u16x8 *>(a.lrow + at));
+            const f32x4 x0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xs + at));
+            const f32x4 x1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(xs + at + 4));
+            // the in-lane run (a pad's candidate -- whatever its column block starts with -- only ever joins a run of pads, which is dropped)
+            const auto cand = [&](int j) { const float xv = j < 4 ? x0[j & 3] : x1[j & 3]; return tp_min_key(PLUS ? (float)v[j] + xv : xv); };
+            unsigned cur = lr[0];
+            unsigned run = cand(0);
+            bool one_run = true;
+#pragma unroll
+            for (int j = 1; j < 8; ++j) {
+                const unsigned r = lr[j];
+                const unsigned p = cand(j);
+                if (r == cur) run = min(run, p);
+                else {
+                    if (cur != kTpPadRow) __hip_atomic_fetch_min(yl + cur, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    cur = r; run = p; one_run = false;
+                }
+            }
+            // ... and the segmented scan across the lanes of one segment, as in dasp_tp_reduce_kernel: one atomic per run of lanes that each hold one run of the same row
+            const unsigned key = one_run && cur != kTpPadRow ? cur : 0x10000u + (unsigned)lane;
+            const int ls = lane % LPS;
+#define DASP_TP_SCAN(D, CTRL) if constexpr (D < LPS) { const unsigned k2 = dpp_mov_u32<CTRL>(key); const unsigned r2 = dpp_mov_u32<CTRL>(run); if (ls >= D && k2 == key) run = min(run, r2); }
+            DASP_TP_SCAN(1, 0x111) DASP_TP_SCAN(2, 0x112) DASP_TP_SCAN(4, 0x114)
+#undef DASP_TP_SCAN
+            const unsigned knext = dpp_mov_u32<0x101>(key);       // row_shl:1
+            const bool last = ls == LPS - 1 || knext != key;
+            if (cur != kTpPadRow && last) __hip_atomic_fetch_min(yl + cur, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    __syncthreads();
+    if (acc) { for (int i = threadIdx.x; i < rows; i += 512) y[p0 + i] = tp_min_unkey(min(tp_min_key(y[p0 + i]), yl[i])); }
+    else for (int i = threadIdx.x; i < rows; i += 512) y[p0 + i] = tp_min_unkey(yl[i]);
+}
+
+// The hub rows: the grid, units, f32 slice of x in LDS, 16-byte loads and U = 4 steps in flight of dasp_lcb_f32_kernel.  A lane takes the min of its 8 candidates
+// (pads skipped), the 16 lanes of a step combine by the same row_ror moves on one dword, lane 0 parks the step's minimum in LDS (4 bytes per step); one thread per
+// piece takes the min of its steps and stores an f32 partial into the LOW 4 BYTES of the piece's 8-byte slot of DevicePlan::wide_part.  (Not a dense float view of
+// that buffer: piece q's float would land in the slot of piece q / 2, and the slots of pieces that belong to no unit must keep the zero fill that
+// dasp_plan_spmv_f32 relies on.  The slots written here are rewritten whole by dasp_lcb_f32_kernel before it reads them.)  No atomics.
+template <bool PLUS>
+__global__ __launch_bounds__(1024) void dasp_lcb_min_f32_kernel(LcbDev a, const float *__restrict__ x)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    constexpr int A = 8;
+    typedef _Float16 vecA __attribute__((ext_vector_type(A)));
+    typedef unsigned short colA __attribute__((ext_vector_type(A)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    float *xl = reinterpret_cast<float *>(lds_raw);
+    const int u = blockIdx.x;
+    const int c = a.unit[3 * u], q0 = a.unit[3 * u + 1], q1 = a.unit[3 * u + 2];
+    const int c0 = c * a.cb, len = min(a.cb, a.xlen - c0);
+    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {          // (c0 is a multiple of 4 elements)
+        for (int i = threadIdx.x * 4; i < len; i += 1024 * 4) {
+            if (i + 4 <= len) *reinterpret_cast<f32x4 *>(xl + i) = *reinterpret_cast<const f32x4 *>(x + c0 + i);
+            else for (int j = i; j < len; ++j) xl[j] = x[c0 + j];
+        }
+    } else for (int i = threadIdx.x; i < len; i += 1024) xl[i] = x[c0 + i];
+    __syncthreads();
+    constexpr int G = kLcbStep / A, SPW = 64 / G;         // 16 lanes per step, four steps per wave instruction
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane / G, l = lane % G;
+    unsigned *stepmin = reinterpret_cast<unsigned *>(lds_raw + (((size_t)a.cb * 4 + 15) & ~size_t(15)));
+    const int np = q1 - q0;
+    const _Float16 *val = static_cast<const _Float16 *>(a.val);
+    const int S0 = a.ptr[q0] / kLcbStep, S1 = a.ptr[q1] / kLcbStep;
+    constexpr int U = 4;
+    for (int sb = S0 + wave * SPW * U; sb < S1; sb += 16 * SPW * U) {
+        vecA v[U] = {}; colA lc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int st = min(sb + u * SPW + g, S1 - 1);          // (a step past the end re-reads the last one; its minimum is dropped below)
+            const size_t e = (size_t)st * kLcbStep + (size_t)l * A;
+            if constexpr (PLUS) v[u] = __builtin_nontemporal_load(reinterpret_cast<const vecA *>(val + e));
+            lc[u] = __builtin_nontemporal_load(reinterpret_cast<const colA *>(a.lcol + e));
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            unsigned s = kMinKeyInf;
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                const bool pad = lc[u][j] == kLcbPadCol;          // pads reach neither x nor the minimum
+                const float xv = xl[pad ? 0 : lc[u][j]];
+                s = min(s, pad ? kMinKeyInf : tp_min_key(PLUS ? (float)v[u][j] + xv : xv));
+            }
+            s = min(s, dpp_mov_u32<0x128>(s)); s = min(s, dpp_mov_u32<0x124>(s)); s = min(s, dpp_mov_u32<0x122>(s)); s = min(s, dpp_mov_u32<0x121>(s));      // row_ror 8, 4, 2, 1
+            if (l == 0 && sb + u * SPW + g < S1) stepmin[sb + u * SPW + g - S0] = s;
+        }
+    }
+    __syncthreads();
+    float *partial = static_cast<float *>(a.partial);
+    for (int i = threadIdx.x; i < np; i += 1024) {
+        unsigned s = kMinKeyInf;
+        for (int st = a.ptr[q0 + i] / kLcbStep - S0, se = a.ptr[q0 + i + 1] / kLcbStep - S0; st < se; ++st) s = min(s, stepmin[st]);
+        partial[2 * (size_t)(q0 + i)] = tp_min_unkey(s);
+    }
+}
+// one workgroup per hub row: the min over the row's column blocks, thread-strided, per wave and then over the four waves through LDS, and into y BEHIND phase 2 (which
+// stored +inf there, or left y_old in accumulate mode): y[dst] = min(y[dst], s).  A piece WITHOUT elements (ptr[q + 1] == ptr[q]) is skipped: a run of such pieces
+// belongs to no unit (lcb_units), no kernel ever writes its slot, and it keeps the zero fill that dasp_plan_spmv_f32 relies on -- reading it would put a 0 into the minimum.
+__global__ __launch_bounds__(256) void dasp_lcb_reduce_min_f32_kernel(LcbDev a, float *__restrict__ y)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];          // dynamic: kWavesPerWG x 4 bytes
+    unsigned *wmin = reinterpret_cast<unsigned *>(lds_raw);
+    static_assert(kWavesPerWG == 4, "four waves per workgroup");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x;
+    const float *partial = static_cast<const float *>(a.partial);
+    unsigned s = kMinKeyInf;
+    for (int c = threadIdx.x; c < a.n_cb; c += 256) {
+        const size_t q = (size_t)c * (size_t)a.n_rows + (size_t)i;
+        if (a.ptr[q + 1] != a.ptr[q]) s = min(s, tp_min_key(partial[2 * q]));
+    }
+    s = min(s, dpp_mov_u32<0x128>(s)); s = min(s, dpp_mov_u32<0x124>(s)); s = min(s, dpp_mov_u32<0x122>(s)); s = min(s, dpp_mov_u32<0x121>(s));
+    s = min(min((unsigned)__builtin_amdgcn_readlane((int)s, 0), (unsigned)__builtin_amdgcn_readlane((int)s, 16)),
+            min((unsigned)__builtin_amdgcn_readlane((int)s, 32), (unsigned)__builtin_amdgcn_readlane((int)s, 48)));
+    if (lane == 0) wmin[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) { const int d = a.row_dst[i]; y[d] = tp_min_unkey(min(min(tp_min_key(y[d]), min(wmin[0], wmin[1])), min(wmin[2], wmin[3]))); }
+}
+
 #ifdef DASP_STAMPS
 int g_stamp_launch = -1;          // host: the number the next stamped launch carries (-1: stamps off)
 }  // namespace dasp
@@ -920,7 +1079,11 @@ int tp_kernels_allow_lds()
                            reinterpret_cast<const void *>(&dasp_lcb_kernel<_Float16>), reinterpret_cast<const void *>(&dasp_lcb_kernel<double>), reinterpret_cast<const void *>(&dasp_lcb_exact_kernel),
                            // f32 vectors (dasp_plan_spmv_f32): an f32 slice of x is twice the f16 one
                            reinterpret_cast<const void *>(&dasp_tp_expand_kernel<float>), reinterpret_cast<const void *>(&dasp_tp_reduce_f32_kernel), reinterpret_cast<const void *>(&dasp_lcb_f32_kernel),
-                           reinterpret_cast<const void *>(&dasp_lcb_reduce_f32_kernel)})
+                           reinterpret_cast<const void *>(&dasp_lcb_reduce_f32_kernel),
+                           // min-plus / min-second products (dasp_plan_spmv_semiring_f32): the same f32 slice of x
+                           reinterpret_cast<const void *>(&dasp_tp_reduce_min_f32_kernel<true>), reinterpret_cast<const void *>(&dasp_tp_reduce_min_f32_kernel<false>),
+                           reinterpret_cast<const void *>(&dasp_lcb_min_f32_kernel<true>), reinterpret_cast<const void *>(&dasp_lcb_min_f32_kernel<false>),
+                           reinterpret_cast<const void *>(&dasp_lcb_reduce_min_f32_kernel)})
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return DASP_OK;
 }
@@ -1050,6 +1213,40 @@ int launch_spmv_f32(Plan &p, const float *dX, float *dY, void *stream, bool accu
     if (a.n_units > 0) hipLaunchKernelGGL((dasp_tp_expand_kernel<float>), dim3(a.n_units), dim3(512), (size_t)a.cb * 4, s, a, dX);
     if (a.n_rb > 0) hipLaunchKernelGGL(dasp_tp_reduce_f32_kernel, dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 8, s, a, dY, accumulate ? 1 : 0);
     if (hub) hipLaunchKernelGGL(dasp_lcb_reduce_f32_kernel, hub_grid, dim3(256), kWavesPerWG * sizeof(double), s, q, dY);
+    HIP_TRY(hipGetLastError());
+    return DASP_OK;
+}
+
+// the hub kernel of the min products: the f32 slice of x, 16 bytes of alignment slack, and 4 bytes per step of the longest possible unit (a piece's minimum is taken
+// by one thread straight from the step words: no per-piece scratch)
+static size_t lcb_min_lds_bytes(const LcbDev &q) { return (size_t)q.cb * 4 + 16 + (size_t)(kLcbUnitElems / kLcbStep + kLcbUnitPieces) * 4; }
+
+// y_i = min_j (a_ij + x_j) / min_j x_j (accumulate: min(y_old_i, that)) with f32 vectors (dasp_plan_spmv_semiring_f32): the launch order and the device views of launch_spmv_f32 --
+// hub stream kernel, phase 1, phase 2, hub reduce; x is read by the first two only, y is first stored by the third, so dX == dY is allowed.  Nothing is allocated:
+// the product runs over the wide xs and the hub partial buffer of the f32-vector mode.
+template <bool PLUS>
+static void launch_semiring_kernels(const TpDev &a, const LcbDev &q, bool hub, const float *dX, float *dY, hipStream_t s, int acc)
+{
+    if (hub) hipLaunchKernelGGL((dasp_lcb_min_f32_kernel<PLUS>), dim3(q.n_units), dim3(1024), lcb_min_lds_bytes(q), s, q, dX);
+    if (a.n_units > 0) hipLaunchKernelGGL((dasp_tp_expand_kernel<float>), dim3(a.n_units), dim3(512), (size_t)a.cb * 4, s, a, dX);
+    if (a.n_rb > 0) hipLaunchKernelGGL((dasp_tp_reduce_min_f32_kernel<PLUS>), dim3(a.n_rb), dim3(512), (size_t)a.rb_max * 4, s, a, dY, acc);
+    if (hub) hipLaunchKernelGGL(dasp_lcb_reduce_min_f32_kernel, dim3(q.n_rows), dim3(256), kWavesPerWG * sizeof(unsigned), s, q, dY);
+}
+int launch_spmv_semiring_f32(Plan &p, int semiring, const float *dX, float *dY, void *stream, bool accumulate)
+{
+    if (!p.dev || !p.dev->arena) { set_error("plan not uploaded"); return DASP_ERR_STATE; }
+    if (!p.two_phase || !p.f32_vectors || !p.dev->wide_xs) { set_error("f32 vectors are off: call dasp_plan_set_f32_vectors(plan, 1) first"); return DASP_ERR_STATE; }
+    if (!dX || !dY) { set_error("null device pointer"); return DASP_ERR_ARG; }
+    if (semiring != DASP_MIN_PLUS && semiring != DASP_MIN_SECOND) { set_error("semiring must be DASP_MIN_PLUS or DASP_MIN_SECOND"); return DASP_ERR_ARG; }
+    const bool hub = p.lcb.n_rows() > 0;
+    if (hub && !p.dev->wide_part) { set_error("f32 vectors: the plan has no hub partial buffer"); return DASP_ERR_STATE; }
+    TpDev a = p.dev->tp;
+    a.xs = p.dev->wide_xs;
+    LcbDev q = p.dev->lcb;
+    q.partial = p.dev->wide_part; q.xpart = nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (semiring == DASP_MIN_PLUS) launch_semiring_kernels<true>(a, q, hub, dX, dY, s, accumulate ? 1 : 0);
+    else launch_semiring_kernels<false>(a, q, hub, dX, dY, s, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return DASP_OK;
 }

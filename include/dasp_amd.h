@@ -458,6 +458,31 @@ int dasp_plan_f32_vectors(const dasp_plan_t *plan);
 int dasp_plan_spmv_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream);
 int dasp_plan_spmv_acc_f32(dasp_plan_t *plan, const float *dX, float *dY, void *stream);
 
+/* Min-plus products on the same plan: shortest-path relaxations (Bellman-Ford), BFS levels, label propagation -- the sweep of dasp_plan_spmv_f32 over the same packed
+ * streams with another pair of operations (no reference counterpart).  The plan, its arena, plan files and the value map are untouched: launch-time only. */
+typedef enum { DASP_MIN_PLUS = 1, DASP_MIN_SECOND = 2 } dasp_semiring;
+/* y = A (x) x over (min, +) / (min, second) with f32 vectors on an f16 two-phase plan
+ * dX holds dasp_plan_x_len floats, dY rowA floats in the plan's y_order, both device pointers.
+ * DEFINED RESULT, for every row i, over the STORED entries of the row:
+ *   DASP_MIN_PLUS    p_j = (float)a_ij + x_j: one f32 addition, round to nearest (the f16 to f32 conversion is exact);
+ *   DASP_MIN_SECOND  p_j = x_j: the stored value is ignored, only the pattern counts;
+ *   accumulate = 0   y_i = min_j p_j; a row without stored entries gives +inf;
+ *   accumulate = 1   y_i = min(y_old_i, min_j p_j) -- the Bellman-Ford relaxation; a row without entries keeps y_old.
+ * EVERY stored entry takes part, duplicates and entries with a_ij = 0 included: a stored zero is an edge of length 0, not an absent edge.  Pad elements of the packed
+ * arrays never take part (they are known by their local row / column, never by their value).  x may hold +-inf (+inf: an unreached vertex); a is finite.  With a NaN
+ * anywhere in a row (in x, in a, or in y_old when accumulating) that row's result is unspecified, but the same in every run.  The sign of a zero result is unspecified:
+ * compare values, not bits.  min is associative, commutative and exact, so the result does not depend on the run, on tp_col_block / tp_row_block, on y_order, or on
+ * whether the host or the device packer built the plan.  dasp_plan_set_tp_exact / dasp_plan_set_hub_exact are ignored: there is nothing to make exact.
+ * dX == dY is allowed (in-place Bellman-Ford on a square DASP_Y_NATURAL plan: a buffer of max(rowA, dasp_plan_x_len) floats, accumulate = 1): the launch reads x only
+ * in kernels that complete, in stream order, before the first store to y -- hub stream kernel, then phase 1, then phase 2 (first store), then hub reduce.
+ * Checked in this order:
+ *   DASP_ERR_ARG    NULL plan, NULL dX or dY;
+ *   DASP_ERR_ARG    semiring not one of the two, accumulate not 0 or 1, or a borrowed panel handle;
+ *   DASP_ERR_STATE  unless dasp_plan_set_f32_vectors(plan, 1) has succeeded: the product runs over exactly that mode's wide xs and, for a hybrid, its hub partial buffer.
+ * It allocates nothing of its own.  Asynchronous on `stream`, kernel launches only (capture-safe).  One product in flight per plan; it may alternate freely with
+ * dasp_plan_spmv, dasp_plan_spmv_f32 and dasp_plan_update_values on one stream (refreshed values reach DASP_MIN_PLUS: it reads the same packed values). */
+int dasp_plan_spmv_semiring_f32(dasp_plan_t *plan, int semiring, const float *dX, float *dY, int accumulate, void *stream);
+
 /* the reference's timing protocol (dasp_f64.h:1285-1320,1394): `warmup` untimed + `iters`
  * timed back-to-back SpMVs on `stream`, one sync at the end.
  * wall_ms_per_iter: host clock; event_ms_per_iter: hipEvent pair recorded on `stream`. */
