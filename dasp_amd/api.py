@@ -18,6 +18,10 @@ from ._lib import DaspError, Options, Stats
 
 Y_PERMUTED, Y_NATURAL = 0, 1
 MIN_PLUS, MIN_SECOND = 1, 2      # dasp_semiring (Plan.spmv_semiring_f32)
+# the ints of Plan.launch_shape, in order: (name, how many)
+SHAPE_FIELDS = (("nt", 1), ("win1", 1), ("seven_waves", 1), ("long16", 1), ("shared_ids", 1), ("wpw", 1), ("wg_long", 1), ("wg_med", 1), ("wg_short", 1), ("wg_rt", 1),
+                ("wg_rot", 1), ("win_tiles", 1), ("win_xcd", 1), ("short_tpw", 1), ("n_short_waves", 1), ("grp_wave0", 33), ("med_stride", 1), ("xcd_on", 1), ("xcd_blk", 9),
+                ("ywt", 1))
 
 
 def _vp(a):
@@ -301,6 +305,16 @@ class Plan:
         if name is None:
             raise _lib.DaspError(-22, _lib.lib().dasp_last_error().decode("utf-8", "replace"))
         return name.decode()
+
+    def launch_shape(self, cus=256, f16_resident=0, uploaded=False):
+        """The plan's launch shape (launch_shape.cpp) as a list of ints in the order of SHAPE_FIELDS.  uploaded=False: what an upload on a
+        device of `cus` compute units holding `f16_resident` workgroups of the f16 kernel per CU (0: unknown) would decide now, environment knobs included -- no
+        GPU needed.  uploaded=True: what the uploaded plan carries."""
+        out = (C.c_int * 128)()
+        n = _lib.lib().dasp_debug_plan_launch_shape(self._h, int(cus), int(f16_resident), int(bool(uploaded)), out, 128)
+        if n < 0:
+            _lib.check(n)
+        return list(out[:n])
 
     def set_stream_policy(self, policy):
         """0 auto, 1 plain loads (reference dasp_spmv), 2 non-temporal loads (reference dasp_spmv2 'bypass')."""

@@ -68,6 +68,8 @@ struct DevArgs {
     // med_shtab = one 16-byte entry per block {ranks lo, ranks hi, offset into the plane / 16, L}.  Null unless the plan launches dasp_spmv_shared_kernel (DevicePlan::shared_ids), the only kernel that reads them
     const unsigned char *med_shplane; const unsigned *med_shtab;
 };
+// the step kernels take the block by value and the device copy is read at fixed offsets: a field is added at the end or not at all
+static_assert(sizeof(DevArgs) == 728 && offsetof(DevArgs, med_shtab) == 720, "DevArgs: the layout the kernels were built against has moved");
 
 // two-phase form (plan.hpp struct TwoPhase): what its two kernels read.  All device pointers into the plan's arena; xs is the stream phase 1
 // writes and phase 2 reads (one x value per stored element)
@@ -123,8 +125,11 @@ struct DevicePlan {
     // r6: >= 5 % of the plan's nonzeros sit in narrow long pieces (plan.hpp long_cid16) of a plain plan: launch the builds that read their 16-bit ids (kernels.hip L16)
     bool long16 = false;
     // r7: the arena holds the shared id plane (DevArgs::med_shplane) and the launch uses the kernel that reads it (kernels.hip dasp_spmv_shared_kernel): f64 plans that stream
-    // from HBM and whose twin rows save >= 3 % of the streamed bytes (upload.cpp shared_ids_rule)
+    // from HBM and whose twin rows save >= 3 % of the streamed bytes (launch_shape.cpp shared_ids_rule)
     bool shared_ids = false;
+    // what DevArgs::ywt is at a launch, before the DASP_Y_WT knob (launch_shape.cpp).  Here and not in `args`: it follows nt, which dasp_plan_set_stream_policy may change
+    // between two launches, and a changed `args` would be re-sent to the device by the next launch -- a blocking copy, possibly inside a stream capture
+    bool ywt = false;
     int device = -1;
     // column-panel parent: arena = the panels' partial results, panel k at ypart + k * ypart_stride elements
     size_t ypart_stride = 0;
@@ -145,8 +150,28 @@ void value_map_free(DevicePlan *d);    // devpack.hip
 
 int require_device();                  // upload.cpp: DASP_OK, or DASP_ERR_NO_DEVICE with the error text set
 int upload_plan(Plan &p);
-void choose_long16(Plan &p);           // upload.cpp
-long long shared_ids_net_saving(const Plan &p, const SharedIds &s, bool long16);      // upload.cpp: streamed bytes the shared plane saves (choose rule)
+
+// ---- launch_shape.cpp: everything an upload DECIDES about a plan's launches, as one pure host function (no HIP call; DESIGN.md section 4 has the table of rules).
+// The two facts about the device the rules read: its CU count (256 where the query fails) and the workgroups of the non-windowed f16 kernel a CU holds (0: unknown)
+struct DeviceFacts { int cus = 256; int f16_resident = 0; };
+struct LaunchShape {
+    bool nt = false, win1 = false, seven_waves = false, long16 = false, shared_ids = false;      // DevicePlan's flags: the key of the kernel table (kernels.hip select_spmv_variant)
+    int wpw = 0, wg_long = 0, wg_med = 0, wg_short = 0, wg_rt = 0, wg_rot = 0, win_tiles = 0, win_xcd = 0, short_tpw = 0, n_short_waves = 0;      // DevArgs' fields of the same names
+    int grp_wave0[kNumShortGroups] = {};
+    int med_stride = 0, xcd_on = 0, xcd_blk[9] = {};
+    bool ywt = false;       // DevicePlan::ywt
+};
+// the A/B knobs of the rules, read from the environment at every upload (never cached: the tools flip them between two uploads of one process)
+struct Knob { bool set = false; int v = 0; };
+struct ShapeKnobs { Knob long16, seven_waves, share_ids, win_xcd, win1, med_loop, xcd_blocks, wg_rot, win_fold; };      // DASP_LONG16 ... DASP_WIN_FOLD
+ShapeKnobs read_knobs();
+bool y_wt_knob_allows();               // DASP_Y_WT, the tenth: read at every LAUNCH (tools/ywt_ab.py flips it between two launches of one plan); false only for DASP_Y_WT=0
+bool wants_shared_ids(const Plan &p);  // does an upload of this plan derive the shared id plane at all?  (it streams from HBM, or DASP_SHARE_IDS=1; never under DASP_SHARE_IDS=0)
+bool f16_persistent_set(const Plan &p);      // does the plan take the persistent medium range of uniform f16 blocks?  (the one rule that reads DeviceFacts::f16_resident)
+LaunchShape launch_shape(const Plan &p, const DeviceFacts &dev, const SharedIds *sh);      // sh: the derived plane, null where there is none
+void apply(const LaunchShape &s, DevicePlan &d);
+void choose_long16(Plan &p);           // DevicePlan::long16 again, once the device packer has sent the pieces' narrow flags back
+int set_stream_policy(Plan &p, int policy);
 int sync_dev_args(Plan &p);            // upload.cpp: DevicePlan::dargs = DevicePlan::args (a memcmp when nothing changed; a blocking copy otherwise -- never inside a stream capture: upload and the placement trials leave it in sync)
 int upload_plan_unpacked(Plan &p);     // for the device packers: arena + O(rows) arrays, no placement trials yet
 // kernels.hip: one SpMV of an uploaded plan (asynchronous); what upload.cpp asks the kernels

@@ -1013,7 +1013,7 @@ const SpmvVariant &select_spmv_variant(const VariantKey &k)
     unsigned bits = (k.nt ? kVNt : 0u) | (k.c16 ? kVC16 : 0u);
     if (k.row_tiles) bits |= kVRt;                                              // a column panel with row tiles (never windowed, never with one-byte ids: plan.cpp build_panels)
     else if (k.windowed && k.win1 && !k.nt) bits |= kVWin1;                     // at most one window workgroup per CU: the 128-register build
-    else if (f64 && k.c16 && plain && k.shared_ids) bits |= kVC8 | kVShared;    // twin rows share their ids (upload.cpp): the one-byte-id build over the shared plane
+    else if (f64 && k.c16 && plain && k.shared_ids) bits |= kVC8 | kVShared;    // twin rows share their ids (launch_shape.cpp): the one-byte-id build over the shared plane
     else if (f64 && k.c16 && plain && k.has_reg8) bits |= kVC8 | (k.seven_waves ? kVSeven : 0u);      // plans with one-byte ids: their own instantiation
     else if (plain && k.long16 && !(f64 && k.seven_waves)) bits |= kVL16;       // narrow long pieces that matter: the builds that read their 16-bit ids
     else if (f64 && plain && k.seven_waves) bits |= kVSeven;
@@ -1059,17 +1059,6 @@ static int launch_typed(Plan &p, const DevArgs &a, hipStream_t s)
     }
     if (a.n_multi > 0) hipLaunchKernelGGL((dasp_long_reduce_kernel<T>), dim3(a.n_multi), dim3(256), 0, s, c);
     HIP_TRY(hipGetLastError());
-    return DASP_OK;
-}
-
-int set_stream_policy(Plan &p, int policy)
-{
-    if (policy < 0 || policy > 2) { set_error("stream_policy must be 0, 1 or 2"); return DASP_ERR_ARG; }
-    p.opt.stream_policy = policy;
-    if (p.dev) p.dev->nt = policy == 2 || (policy != 1 && p.stats.data_X > kStreamBytes);
-    // panels follow the whole matrix: auto means non-temporal when the sum of the panels streams from HBM
-    const int sub = policy != 0 ? policy : (p.stats.data_X > kStreamBytes ? 2 : 1);
-    for (auto &h : p.panels) if (int rc = set_stream_policy(h->impl, sub)) return rc;
     return DASP_OK;
 }
 
@@ -1186,9 +1175,7 @@ int launch_spmv(Plan &p, const void *dX, void *dY, void *stream, bool accumulate
     }
     DevArgs a = p.dev->args;
     a.x = dX; a.y = dY; a.acc = accumulate ? 1 : 0;
-    // one block / tile / piece per wave and then the wave ends: f64 plans without x windows and without a striding medium range
-    a.ywt = p.dev->nt && p.precision == 64 && !p.windowed && !a.med_stride && !p.panel ? 1 : 0;
-    if (const char *e = std::getenv("DASP_Y_WT")) a.ywt = a.ywt && std::atoi(e) != 0;      // A/B knob
+    a.ywt = p.dev->ywt && y_wt_knob_allows() ? 1 : 0;      // (the rule: launch_shape.cpp; the knob is read at every launch)
     hipStream_t s = static_cast<hipStream_t>(stream);
     return p.precision == 64 ? launch_typed<double>(p, a, s) : launch_typed<_Float16>(p, a, s);
 }
@@ -1267,6 +1254,8 @@ extern "C" const char *dasp_debug_plan_kernel(const dasp_plan_t *plan)
     const dasp::DevArgs &a = p.dev->args;
     return p.two_phase ? "two_phase" : !p.panels.empty() ? "panels" : a.wg_long + a.wg_med + a.wg_short + a.wg_rt > 0 ? dasp::select_spmv_variant(dasp::variant_key(p, *p.dev)).name : "none";
 }
+// the second device fact behind a plan's launch shape (launch_shape.cpp DeviceFacts::f16_resident), as upload asks for it; needs a device
+extern "C" int dasp_debug_f16_resident(int c16) { return dasp::spmv_kernel_f16_resident(c16 != 0); }
 namespace dasp {
 
 namespace {

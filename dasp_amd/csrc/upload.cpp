@@ -1,6 +1,6 @@
 // upload.cpp -- a packed plan's way onto the device: one arena for every array (dasp_f64.h:1239-1278 does one cudaMalloc + cudaMemcpy per
-// array), the launch geometry that goes with it, and the placement trials (profiles/r03_placement.md).  Host code only; the kernels it
-// asks about live in kernels.hip (spmv_kernel_* below).
+// array) and the placement trials (profiles/r03_placement.md).  What the launches look like is decided in launch_shape.cpp and applied here.
+// Host code only; the kernels it asks about live in kernels.hip (spmv_kernel_* below).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -103,66 +103,6 @@ static int upload_long_cb(Plan &p, DevicePlan *d, const LcbOffsets &o)
     return DASP_OK;
 }
 
-// DevicePlan::long16 from the pieces' narrow flags (host-built plans: at upload; device-built ones: again once the device packer has sent the flags back)
-static bool long16_rule(const Plan &p, long long *narrow_elems)
-{
-    bool on = false;
-    long long narrow = 0;
-    if (!p.windowed && p.cnt_reg8 == 0 && p.piece_c16.size() == 2 * p.piece_dst.size() && !p.piece_dst.empty()) {
-        for (size_t q = 0; q < p.piece_dst.size(); ++q) if (p.piece_c16[2 * q + 1]) narrow += p.piece_ptr[q + 1] - p.piece_ptr[q];
-        on = narrow * 20 >= (long long)p.nnz && narrow > 0;
-        if (const char *e = std::getenv("DASP_LONG16")) on = std::atoi(e) != 0;      // A/B knob
-    }
-    if (narrow_elems) *narrow_elems = narrow;
-    return on;
-}
-void choose_long16(Plan &p)
-{
-    DevicePlan *d = p.dev;
-    if (!d) return;
-    d->long16 = long16_rule(p, nullptr);
-}
-
-// r7, the shared id plane (plan.hpp struct SharedIds): streamed bytes per SpMV it saves -- the id bytes of the paired regions minus the plane and its table, minus 2 bytes
-// per element of the narrow long pieces where the plan would otherwise run the build that reads their 16-bit ids (the shared build reads the 32-bit ones)
-long long shared_ids_net_saving(const Plan &p, const SharedIds &s, bool long16)
-{
-    long long narrow = 0;
-    (void)long16_rule(p, &narrow);
-    return s.paired_id_bytes - s.shared_bytes - (long16 ? 2 * narrow : 0);
-}
-// DevicePlan::seven_waves (device.hpp): most of the regular chunks sit in one-shot blocks of a bandwidth-bound f64 plan
-static bool seven_waves_rule(const Plan &p)
-{
-    bool on = false;
-    if (p.precision == 64 && !p.windowed && p.med_ptr.size() > 1 && p.irr_ptr.size() > 1) {
-        long long one = 0, all = 0;
-        const int K = p.geo.med_k, nbk = (int)p.med_ptr.size() - 1;
-        for (int b = 0; b < nbk; ++b) {
-            const int nc = p.med_ptr[(size_t)b + 1] - p.med_ptr[(size_t)b], r0 = b * kMedRows;
-            const int nt = (p.irr_ptr[(size_t)r0 + 1] - p.irr_ptr[(size_t)r0] + K - 1) / K;
-            all += nc + nt;
-            if (med_oneshot64(nc, nt)) one += nc + nt;
-        }
-        // (bandwidth-bound plans only: webbase-1M f64, 43 MB in 29 us, loses 1.7 % on the 72-register build; nlpkkt160 0.4636 -> 0.4426 ms, x0.1 = 291 MB 41.6 -> 40.7 us)
-        on = all > 0 && one * 10 >= all * 7 && p.stats.data_X > (64ll << 20);
-        if (const char *e = std::getenv("DASP_SEVEN_WAVES")) on = std::atoi(e) != 0;      // A/B knob
-    }
-    return on;
-}
-// is the shared kernel launched?  The plan streams from HBM (the line of the non-temporal policy) and the plane saves >= 3 % of its streamed bytes; DASP_SHARE_IDS=1 / 0
-// (read at upload) forces it on wherever a plane can be derived / off
-static int share_ids_env() { const char *e = std::getenv("DASP_SHARE_IDS"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }
-static bool shared_ids_rule(const Plan &p, const SharedIds &s)
-{
-    // a plan of one-shot blocks keeps the 7-wave build (seven_waves_rule, DASP_SEVEN_WAVES=1 included): the shared kernel is the 6-wave one-byte-id build, and what it
-    // saves lies in pipelined blocks, which such a plan hardly has
-    if (seven_waves_rule(p)) return false;
-    const int env = share_ids_env();
-    if (env >= 0) return env == 1;
-    return p.stats.data_X > kStreamBytes && shared_ids_net_saving(p, s, long16_rule(p, nullptr)) * 100 >= 3 * p.stats.data_X;
-}
-
 void release_device(Plan &p)
 {
     if (p.dev) {
@@ -216,64 +156,73 @@ int set_f32_vectors_device(Plan &p, int on)
 }
 
 int upload_plan(Plan &p);
-static int upload_plan_impl(Plan &p)
+// column panels: every panel is a plan of its own; this one only owns their partial results
+static int upload_panel_parent(Plan &p, DevicePlan *d)
 {
-    if (int rc = require_device()) return rc;
-    if (p.host_dropped && p.dev) return DASP_OK;   // already on the device (packed there, or host copies released)
-    if (p.host_dropped) { set_error("host arrays were dropped"); return DASP_ERR_STATE; }
-    release_device(p);
-    auto *d = new DevicePlan();
-    p.dev = d;
-    HIP_TRY(hipGetDevice(&d->device));
-    if (!p.panels.empty()) {   // column panels: every panel is a plan of its own; this one only owns their partial results
-        for (auto &h : p.panels) if (int rc = upload_plan(h->impl)) return rc;
-        d->ypart_stride = ((size_t)std::max(p.m, 1) + 127) & ~size_t(127);
-        const size_t part_bytes = d->ypart_stride * p.panels.size() * (size_t)p.geo.vbytes;
-        // column-blocked long rows (Plan::lcb): their streams, tables and partial sums behind the partial-result buffers
-        const LongCB &L = p.lcb;
-        const size_t vbytes = (size_t)p.geo.vbytes;
-        size_t total = (part_bytes + 255) & ~size_t(255);
-        auto place = [&](size_t bytes) { const size_t off = total; total += (std::max<size_t>(bytes, 16) + 255) & ~size_t(255); return off; };
-        const bool lcb = L.n_rows() > 0;
-        LcbOffsets lo;
-        if (lcb) lo = place_long_cb(L, vbytes, place);
-        d->arena_bytes = total;
-        HIP_TRY(hipMalloc(&d->arena, d->arena_bytes));
-        HIP_TRY(hipMemset(d->arena, 0, d->arena_bytes));      // the panels never store the rows that are empty in them (DevArgs::skip0); empty (row, block) pieces never write their partial sum
-        if (lcb) if (int rc = upload_long_cb(p, d, lo)) return rc;
-        return DASP_OK;
-    }
+    for (auto &h : p.panels) if (int rc = upload_plan(h->impl)) return rc;
+    d->ypart_stride = ((size_t)std::max(p.m, 1) + 127) & ~size_t(127);
+    const size_t part_bytes = d->ypart_stride * p.panels.size() * (size_t)p.geo.vbytes;
+    // column-blocked long rows (Plan::lcb): their streams, tables and partial sums behind the partial-result buffers
+    const LongCB &L = p.lcb;
+    const size_t vbytes = (size_t)p.geo.vbytes;
+    size_t total = (part_bytes + 255) & ~size_t(255);
+    auto place = [&](size_t bytes) { const size_t off = total; total += (std::max<size_t>(bytes, 16) + 255) & ~size_t(255); return off; };
+    const bool lcb = L.n_rows() > 0;
+    LcbOffsets lo;
+    if (lcb) lo = place_long_cb(L, vbytes, place);
+    d->arena_bytes = total;
+    HIP_TRY(hipMalloc(&d->arena, d->arena_bytes));
+    HIP_TRY(hipMemset(d->arena, 0, d->arena_bytes));      // the panels never store the rows that are empty in them (DevArgs::skip0); empty (row, block) pieces never write their partial sum
+    if (lcb) if (int rc = upload_long_cb(p, d, lo)) return rc;
+    return DASP_OK;
+}
 
-    if (p.two_phase) {
-        // two-phase form: the tile streams + the xs stream between the two kernels, one allocation
-        const TwoPhase &t = p.tp;
-        const size_t S = t.segments, vbytes = (size_t)p.geo.vbytes;
-        struct Item { const void *src; size_t bytes; size_t off; };
-        std::vector<Item> items;
-        size_t total = 0;
-        auto add = [&](const void *src, size_t bytes) { const size_t off = total; items.push_back({src, bytes, off}); total += (std::max<size_t>(bytes, 16) + 255) & ~size_t(255); return off; };
-        const size_t o_lc = add(t.lcol.data(), S * kTpSeg * 2), o_dst = add(t.dst.data(), S * 4), o_un = add(t.unit.data(), t.unit.size() * 4);
-        const size_t o_v = add(t.val.data(), S * kTpSeg * vbytes), o_lr = add(t.lrow.data(), S * kTpSeg * 2), o_xs = add(nullptr, S * kTpSeg * vbytes);
-        const size_t o_r0 = add(t.rb_row0.data(), t.rb_row0.size() * 4), o_s0 = add(t.rb_seg0.data(), t.rb_seg0.size() * 4);
-        const bool lcb = p.lcb.n_rows() > 0;          // the hybrid: hub rows column-blocked beside the streams
-        LcbOffsets lo;
-        if (lcb) lo = place_long_cb(p.lcb, vbytes, [&](size_t bytes) { return add(nullptr, bytes); });
-        HIP_TRY(hipMalloc(&d->arena, total));
-        d->arena_bytes = total;
-        char *base = static_cast<char *>(d->arena);
-        for (const Item &it : items)
-            if (it.src && it.bytes) HIP_TRY(hipMemcpy(base + it.off, it.src, it.bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(base + o_xs, 0, std::max<size_t>(S * kTpSeg * vbytes, 16)));
-        TpDev &q = d->tp;
-        q.lcol = (const unsigned short *)(base + o_lc); q.dst = (const int *)(base + o_dst); q.unit = (const int *)(base + o_un);
-        q.val = base + o_v; q.lrow = (const unsigned short *)(base + o_lr); q.xs = base + o_xs;
-        q.rb_row0 = (const int *)(base + o_r0); q.rb_seg0 = (const int *)(base + o_s0);
-        q.n_units = t.n_units(); q.n_rb = t.n_rb(); q.cb = t.cb; q.rb_max = t.rb_max; q.xlen = p.n; q.m = p.m;
-        d->nt = true;
-        if (lcb) if (int rc = upload_long_cb(p, d, lo)) { release_device(p); return rc; }      // (the exact partial planes did not fit: nothing is left half-made)
-        return tp_kernels_allow_lds();
-    }
+// two-phase form: the tile streams + the xs stream between the two kernels, one allocation
+static int upload_two_phase(Plan &p, DevicePlan *d)
+{
+    const TwoPhase &t = p.tp;
+    const size_t S = t.segments, vbytes = (size_t)p.geo.vbytes;
+    struct Item { const void *src; size_t bytes; size_t off; };
+    std::vector<Item> items;
+    size_t total = 0;
+    auto add = [&](const void *src, size_t bytes) { const size_t off = total; items.push_back({src, bytes, off}); total += (std::max<size_t>(bytes, 16) + 255) & ~size_t(255); return off; };
+    const size_t o_lc = add(t.lcol.data(), S * kTpSeg * 2), o_dst = add(t.dst.data(), S * 4), o_un = add(t.unit.data(), t.unit.size() * 4);
+    const size_t o_v = add(t.val.data(), S * kTpSeg * vbytes), o_lr = add(t.lrow.data(), S * kTpSeg * 2), o_xs = add(nullptr, S * kTpSeg * vbytes);
+    const size_t o_r0 = add(t.rb_row0.data(), t.rb_row0.size() * 4), o_s0 = add(t.rb_seg0.data(), t.rb_seg0.size() * 4);
+    const bool lcb = p.lcb.n_rows() > 0;          // the hybrid: hub rows column-blocked beside the streams
+    LcbOffsets lo;
+    if (lcb) lo = place_long_cb(p.lcb, vbytes, [&](size_t bytes) { return add(nullptr, bytes); });
+    HIP_TRY(hipMalloc(&d->arena, total));
+    d->arena_bytes = total;
+    char *base = static_cast<char *>(d->arena);
+    for (const Item &it : items)
+        if (it.src && it.bytes) HIP_TRY(hipMemcpy(base + it.off, it.src, it.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(base + o_xs, 0, std::max<size_t>(S * kTpSeg * vbytes, 16)));
+    TpDev &q = d->tp;
+    q.lcol = (const unsigned short *)(base + o_lc); q.dst = (const int *)(base + o_dst); q.unit = (const int *)(base + o_un);
+    q.val = base + o_v; q.lrow = (const unsigned short *)(base + o_lr); q.xs = base + o_xs;
+    q.rb_row0 = (const int *)(base + o_r0); q.rb_seg0 = (const int *)(base + o_s0);
+    q.n_units = t.n_units(); q.n_rb = t.n_rb(); q.cb = t.cb; q.rb_max = t.rb_max; q.xlen = p.n; q.m = p.m;
+    apply(launch_shape(p, DeviceFacts{}, nullptr), *d);
+    if (lcb) if (int rc = upload_long_cb(p, d, lo)) { release_device(p); return rc; }      // (the exact partial planes did not fit: nothing is left half-made)
+    return tp_kernels_allow_lds();
+}
 
+// the two facts about the device the launch shape reads, asked for only where a rule reads them: the CU count for windowed plans and the f16 persistent set, the resident
+// workgroups for the latter
+static DeviceFacts device_facts(const Plan &p, int device)
+{
+    DeviceFacts f;
+    const bool persistent = f16_persistent_set(p);
+    hipDeviceProp_t prop;
+    if ((p.windowed || persistent) && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) f.cus = prop.multiProcessorCount;
+    if (persistent) { f.f16_resident = spmv_kernel_f16_resident(p.cid16); (void)hipGetLastError(); }
+    return f;
+}
+
+// every other form (long pieces, medium blocks, short tiles, row tiles; plain or windowed): lay out, allocate, copy, wire the pointers, apply the launch shape
+static int upload_row_forms(Plan &p, DevicePlan *d)
+{
     std::vector<ShortDev> groups(kNumShortGroups);
     for (int g = 0; g < kNumShortGroups; ++g) {
         groups[g].len = p.grp[g].len; groups[g].count = p.grp[g].count; groups[g].tiles = p.grp[g].tiles;
@@ -343,18 +292,20 @@ static int upload_plan_impl(Plan &p)
     const size_t o_ord = add(natural ? (ord_mapped.empty() ? p.order.data() : ord_mapped.data()) : nullptr, natural ? p.order.size() * 4 : 0);
     // r7: the shared id plane and its per-block table, derived here from the packed id planes (which stay in the arena: the multi-GPU step kernels, the one-shot blocks, the
     // positions behind the paired region and dasp_plan_download_array read them) -- behind everything else, so that every other array keeps its offset.  Only plans that can
-    // use it pay for the derivation: those that stream from HBM, or any qualifying plan under DASP_SHARE_IDS=1; and only a plan that launches the shared kernel carries the
-    // plane in its arena (0.26-0.45 of the paired id bytes: 0.29 B per nonzero on HV15R) -- every other plan's arena is byte for byte what it was
+    // use it pay for the derivation (wants_shared_ids); and only a plan that launches the shared kernel carries the plane in its arena (0.26-0.45 of the paired id bytes:
+    // 0.29 B per nonzero on HV15R) -- every other plan's arena is byte for byte what it was
     SharedIds sh;
-    size_t o_shp = 0, o_sht = 0;
-    d->shared_ids = false;
-    p.sh_in_use = false;
-    if (share_ids_env() != 0 && (p.stats.data_X > kStreamBytes || share_ids_env() == 1)) {
+    bool carry_plane = false;
+    if (wants_shared_ids(p)) {
         const bool have = derive_shared_ids(p, sh);
         p.sh_paired_bytes = sh.paired_id_bytes; p.sh_shared_bytes = sh.shared_bytes; p.sh_known = true;
-        p.sh_in_use = d->shared_ids = have && shared_ids_rule(p, sh);
-        if (d->shared_ids) { o_shp = add(sh.plane.data(), sh.plane.size() * 4); o_sht = add(sh.table.data(), sh.table.size() * 4); }
+        // (none of the flags reads the device: the arena's size is known before anything is allocated, and the device is asked behind the copies, as ever -- what the
+        // occupancy query loads onto the device lands behind the arena, and where the arena lands decides between the two speeds of profiles/r04_placement.md)
+        carry_plane = have && launch_shape(p, DeviceFacts{}, &sh).shared_ids;
     }
+    p.sh_in_use = carry_plane;
+    size_t o_shp = 0, o_sht = 0;
+    if (carry_plane) { o_shp = add(sh.plane.data(), sh.plane.size() * 4); o_sht = add(sh.table.data(), sh.table.size() * 4); }
 
     HIP_TRY(hipMalloc(&d->arena, total));
     d->arena_bytes = total;
@@ -380,109 +331,17 @@ static int upload_plan_impl(Plan &p)
     a.short_val = base + o_sv; a.short_cid = (const int *)(base + o_sc); a.groups = (const ShortDev *)(base + o_g);
     a.n_short_tiles = p.stats.n_short_tiles;
     a.order = natural ? (const int *)(base + o_ord) : nullptr;
-    a.wpw = p.windowed ? std::min(16, p.row_window / kMedRows) : kWavesPerWG;
-    a.wg_long = (a.n_pieces + a.wpw - 1) / a.wpw;
     a.med_cid16 = (const unsigned short *)(base + o_mc16); a.med_base = (const int *)(base + o_mb);
     a.med_cid8 = (const unsigned char *)(base + o_mc8); a.med_c8ptr = (const int *)(base + o_c8p);
-    a.med_shplane = d->shared_ids ? (const unsigned char *)(base + o_shp) : nullptr; a.med_shtab = d->shared_ids ? (const unsigned *)(base + o_sht) : nullptr;
+    a.med_shplane = carry_plane ? (const unsigned char *)(base + o_shp) : nullptr; a.med_shtab = carry_plane ? (const unsigned *)(base + o_sht) : nullptr;
     a.med_dst = (const int *)(base + o_mdst); a.win_cmin = (const int *)(base + o_wc); a.win_len = (const int *)(base + o_wl);
     a.n_windows = (int)p.win_len.size(); a.blocks_per_win = p.windowed ? p.row_window / kMedRows : 0;
     a.win_hybrid = p.win_hybrid ? 1 : 0; a.win_rel16 = p.win_rel16 ? 1 : 0; a.pair_mode = p.pair_mode;
-    a.win_xcd = 1;
     a.skip0 = p.panel ? 1 : 0;
-    if (const char *e = std::getenv("DASP_WIN_XCD")) a.win_xcd = std::atoi(e);      // A/B knob
-    d->win1 = false;
-    d->seven_waves = false;
-    choose_long16(p);
-    d->seven_waves = seven_waves_rule(p);
-    if (p.windowed) {
-        int cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        d->win1 = a.n_windows <= cus;          // (wg_med below rounds the windows up to a multiple of 8: with 249..256 windows the grid is exactly the 256 CUs)
-        if (const char *e = std::getenv("DASP_WIN1")) d->win1 = d->win1 && std::atoi(e) != 0;
-    }
-    a.wg_med = p.windowed ? (a.n_windows + 7) / 8 * 8 : (a.n_blocks + kWavesPerWG - 1) / kWavesPerWG;      // windows: a whole number per XCD (kernel)
-    // f16 blocks of uniform length: a persistent set of 7 workgroups per CU striding over the blocks amortises the per-wave
-    // set-up that weighs twice as much at 2 bytes per value (nlpkkt160 f16 0.675 -> 0.739 of the roofline, Queen_4147 f16
-    // 0.873 -> 0.927).  Static striding needs equal blocks: with HV15R's 2 % of 3x longer rows it loses 10 %, and in f64 it
-    // loses 3-9 % everywhere, so: f16 only, no windows, longest block <= 1.25 x the mean.
-    if (!p.windowed && p.precision == 16 && a.n_blocks > 256 * 7 * kWavesPerWG) {      // (the threshold: a full set on a 256-CU device)
-        int longest = 0;
-        for (int b = 0; b < a.n_blocks; ++b) longest = std::max(longest, p.med_ptr[(size_t)b + 1] - p.med_ptr[(size_t)b]);
-        const double mean = (double)p.med_ptr[(size_t)a.n_blocks] / (double)a.n_blocks;
-        if (p.cnt_irr * 8 <= p.cnt_reg && mean > 0 && (double)longest <= 1.25 * mean) {
-            // as many persistent workgroups per CU as the kernel's registers let reside at once (7 at <= 72 VGPRs), on every CU of the device
-            int per_cu = 7, cus = 256;
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-            const int fit = spmv_kernel_f16_resident(p.cid16);
-            if (fit > 0) per_cu = std::min(per_cu, fit);
-            (void)hipGetLastError();
-            a.wg_med = std::min(a.wg_med, cus * per_cu);
-        }
-    }
-    // XCD-contiguous block ranges (opt-in: DASP_XCD_BLOCKS=1) for plans of EVEN blocks (FEM / stencil rows: longest block <= 4 x the
-    // mean).  Work of a block = its chunks + 2 (row tables, tail); every XCD gets an eighth of it.  Measured r3 (profiles/r03_xcd_blocks.md):
-    // it removes exactly the traffic it was built for -- nlpkkt160's x pulled through eight L2s, FETCH 3.03 -> 2.54 GB per SpMV, 1.03 ->
-    // 0.86 x the CSR bytes -- but that traffic was Infinity-Cache hits, not HBM reads, and the time does not move (nlpkkt160 0.4051 ->
-    // 0.4105 ms, HV15R 0.4274 -> 0.4227, Queen 0.5089 -> 0.5083, f16 0-1.5 % slower), so it stays off by default.
-    a.xcd_on = 0;
-    for (int &v : a.xcd_blk) v = 0;
-    a.med_stride = a.wg_med * kWavesPerWG < a.n_blocks ? 1 : 0;      // the medium range is a persistent, striding set of workgroups (f16 only today)
-    if (const char *e = std::getenv("DASP_MED_LOOP")) a.med_stride = a.med_stride || std::atoi(e) != 0;      // A/B knob
-    if (!p.windowed && a.wg_med == (a.n_blocks + kWavesPerWG - 1) / kWavesPerWG && a.n_blocks >= 8 * 256 && (int)p.med_ptr.size() == a.n_blocks + 1) {
-        int longest = 0;
-        for (int b = 0; b < a.n_blocks; ++b) longest = std::max(longest, p.med_ptr[(size_t)b + 1] - p.med_ptr[(size_t)b]);
-        const double mean = (double)p.med_ptr[(size_t)a.n_blocks] / (double)a.n_blocks;
-        const char *e = std::getenv("DASP_XCD_BLOCKS");
-        const bool on = e && std::atoi(e) != 0 && (double)longest <= 4.0 * std::max(mean, 1.0);
-        if (on) {
-            auto work_before = [&](int b) { return (long long)p.med_ptr[(size_t)b] + 2ll * b; };
-            const long long total = work_before(a.n_blocks);
-            int most = 0;
-            for (int k = 0; k <= 8; ++k) {
-                int lo = 0, hi = a.n_blocks;                               // first block whose preceding work reaches k / 8 of the total
-                while (lo < hi) { const int mid = (lo + hi) / 2; if (work_before(mid) * 8 < total * k) lo = mid + 1; else hi = mid; }
-                a.xcd_blk[k] = k == 8 ? a.n_blocks : lo;
-            }
-            for (int k = 0; k < 8; ++k) most = std::max(most, a.xcd_blk[k + 1] - a.xcd_blk[k]);
-            a.xcd_on = 1;
-            a.wg_med = 8 * ((most + kWavesPerWG - 1) / kWavesPerWG);
-        }
-    }
-    // wave-segmented groups hold 64 ELEMENTS per tile: one tile per wave leaves a wave's fixed cost (arguments, group tables) and one memory round trip per 768 bytes -- a matrix of
-    // short rows only ran at 0.35 of the roofline.  Such plans (f64, no windows, never the multi-GPU step's) hand kShortTpw consecutive tiles to a wave, all loads issued up front
-    a.short_tpw = p.stats.short_seg && !p.windowed && p.precision == 64 ? kShortTpw : 1;
-    a.n_short_waves = 0;
-    for (int g = 0; g < kNumShortGroups; ++g) { a.grp_wave0[g] = a.n_short_waves; a.n_short_waves += p.grp[g].seg && a.short_tpw > 1 ? (p.grp[g].tiles + a.short_tpw - 1) / a.short_tpw : p.grp[g].tiles; }
-    a.wg_short = (a.n_short_waves + a.wpw - 1) / a.wpw;
-    // windowed plans: a short tile per wave in workgroups of 16 waves puts 16 waves of 64-line gathers on each of a few CUs -- on cop20k_A (104 tiles in 7 workgroups) they
-    // were the last waves of the launch to exit (9.9 us against 7.2 for the median window wave).  Where the tiles are few beside the windows they are folded into the window
-    // workgroups as fillers behind their blocks (spmv_body): tile t goes to window t % n_windows.  One launch-wide rule: all tiles or none.
-    // which category the dispatcher starts with (r6, the f16 builds): workgroups start in index order, and what is dispatched last is the launch's tail.  The f16 short tiles
-    // are the longest-lived waves of a latency-bound launch (webbase-1M f16, per-wave stamps: 4.1 us against 3.0 for a medium block) and stood at the end of the grid:
-    // short tiles first, webbase-1M f16 14.68 -> 13.7 us, x4 65.3 -> 61.6, the uniform variant 15.7 -> 15.1 (f64, measured the same way: 28.9 -> 31.2 -- its short waves
-    // hold four tiles each -- so the f64 builds do not carry the rotation at all; medium blocks first: HV15R x0.1 f64 40.9 -> 39.2, not taken up)
-    a.wg_rot = 0;
-    const bool can_rot = p.precision == 16 && !p.windowed && p.rt_mask.empty() && !p.panel;
-    if (can_rot && a.wg_short > 0 && a.wg_long + a.wg_med > 0) a.wg_rot = a.wg_long + a.wg_med;
-    if (const char *e = std::getenv("DASP_WG_ROT")) {      // A/B knob: 0 = the grid as stored [long | medium | short], 1 = short tiles first, 2 = medium blocks first
-        const int k = std::atoi(e);
-        if (can_rot) a.wg_rot = k == 1 ? a.wg_long + a.wg_med : k == 2 ? a.wg_long : 0;
-    }
-    a.win_tiles = 0;
-    if (p.windowed && win_fold_tiles(a.n_windows, a.n_short_tiles) > 0) {
-        a.win_tiles = win_fold_tiles(a.n_windows, a.n_short_tiles);
-        a.wg_short = 0;
-    }
-    if (const char *e = std::getenv("DASP_WIN_FOLD")) if (std::atoi(e) == 0 && a.win_tiles) { a.win_tiles = 0; a.wg_short = (a.n_short_waves + a.wpw - 1) / a.wpw; }      // A/B knob
     a.rt_val = base + o_rv; a.rt_cid = (const int *)(base + o_rc); a.rt_ptr = (const int *)(base + o_rp);
     a.rt_start = (const unsigned short *)(base + o_rs); a.rt_mask = (const unsigned long long *)(base + o_rm);
-    a.n_rt_tiles = (int)p.rt_mask.size(); a.wg_rt = (a.n_rt_tiles + kWavesPerWG - 1) / kWavesPerWG; a.rt_max = p.rt_max;
-    // streamed-once matrix data bypasses the caches (the reference's ld.global.cs, dasp_f64.h:34-51)
-    // only when it cannot stay resident in the 256 MiB Infinity Cache between two SpMVs anyway.
-    d->nt = p.opt.stream_policy == 2 || (p.opt.stream_policy != 1 && p.stats.data_X > kStreamBytes);
+    a.n_rt_tiles = (int)p.rt_mask.size(); a.rt_max = p.rt_max;
+    apply(launch_shape(p, device_facts(p, d->device), carry_plane ? &sh : nullptr), *d);
     if (p.windowed && p.lds_bytes > 65536) {
         // more than the default 64 KiB of dynamic LDS must be requested per kernel; done here (for both cache-policy
         // variants), not in the launch path, so that dasp_plan_spmv stays free of anything a stream capture would reject
@@ -491,6 +350,18 @@ static int upload_plan_impl(Plan &p)
         if (int rc = spmv_kernel_allow_full_lds(p.precision, p.cid16)) return rc;
     }
     return sync_dev_args(p);
+}
+
+static int upload_plan_impl(Plan &p)
+{
+    if (int rc = require_device()) return rc;
+    if (p.host_dropped && p.dev) return DASP_OK;   // already on the device (packed there, or host copies released)
+    if (p.host_dropped) { set_error("host arrays were dropped"); return DASP_ERR_STATE; }
+    release_device(p);
+    auto *d = new DevicePlan();
+    p.dev = d;
+    HIP_TRY(hipGetDevice(&d->device));
+    return !p.panels.empty() ? upload_panel_parent(p, d) : p.two_phase ? upload_two_phase(p, d) : upload_row_forms(p, d);
 }
 
 

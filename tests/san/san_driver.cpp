@@ -12,6 +12,8 @@
 
 #include "../../include/dasp_amd.h"
 
+extern "C" int dasp_debug_plan_launch_shape(const dasp_plan_t *plan, int cus, int f16_resident, int uploaded, int *out, int cap);      // launch_shape.cpp: a test hook, not in the header
+
 static int fails = 0;
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "CHECK failed %s:%d: %s (%s)\n", __FILE__, __LINE__, #c, dasp_last_error()); ++fails; } } while (0)
 
@@ -72,6 +74,14 @@ static void plans_of(const Csr &c, const std::string &scratch, int tag)
             CHECK(dasp_plan_load(&q, path.c_str()) == 0);
             if (q) { dasp_stats_t s2; CHECK(dasp_plan_stats(q, &s2) == 0 && s2.fill0_nnz_reg == st.fill0_nnz_reg); dasp_plan_destroy(q); }
             std::remove(path.c_str());
+            // the launch shape an upload would decide (launch_shape.cpp: pure host code, compiled in), on two devices' facts; every range is a count
+            for (int cus : {256, 4}) {
+                int shape[128];
+                const int ns = dasp_debug_plan_launch_shape(p, cus, k % 8, 0, shape, 128);
+                CHECK(ns > 27);
+                for (int i = 5; i < 10 && i < ns; ++i) CHECK(shape[i] >= 0);
+            }
+            CHECK(dasp_debug_plan_launch_shape(p, 256, 0, 1, nullptr, 0) < 0);      // (no buffer, and not uploaded)
             CHECK(dasp_plan_upload(p) == DASP_ERR_NO_DEVICE);
             dasp_plan_destroy(p);
             ++k;

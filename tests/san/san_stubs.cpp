@@ -1,6 +1,6 @@
 // tests/san/san_stubs.cpp -- TEST INFRASTRUCTURE for the CPU sanitizer builds (make -C dasp_amd/csrc san / tsan).
 // The host side of the library (plan.cpp planio.cpp mmio.cpp gen.cpp capi.cpp multigpu.cpp) is compiled with -fsanitize and linked with
-// this file INSTEAD of the device objects (kernels.hip, devpack.hip, mgstep.hip, mgx.hip, upload.cpp): every device entry point answers
+// this file INSTEAD of the device objects (kernels.hip, devpack.hip, mgstep.hip, mgx.hip, upload.cpp; launch_shape.cpp makes no HIP call and is compiled in): every device entry point answers
 // "no device", exactly what the real ones answer on a machine without a GPU.  GPU AddressSanitizer is not available on this pool.
 #include <string>
 #include <vector>
@@ -18,7 +18,6 @@ int upload_plan(Plan &) { return nodev(); }
 int upload_plan_unpacked(Plan &) { return nodev(); }
 int tune_placement(Plan &, int, const void *, void *, double *, double *) { return nodev(); }
 int launch_spmv(Plan &, const void *, void *, void *, bool) { return nodev(); }
-int set_stream_policy(Plan &, int) { return nodev(); }
 int selftest_mfma() { return nodev(); }
 int download_array(Plan &, const char *, void *, size_t) { return nodev(); }
 int time_spmv(Plan &, const void *, void *, void *, int, int, double *, double *) { return nodev(); }
