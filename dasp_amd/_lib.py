@@ -163,6 +163,10 @@ def lib():
         L.dasp_plan_shared_ids.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ip]
         L.dasp_plan_shared_ids_export.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
         L.dasp_plan_shared_ids_export.restype = C.c_longlong
+    if hasattr(L, "dasp_plan_pair_mask"):            # (likewise)
+        L.dasp_plan_pair_mask.argtypes = [vp, ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.dasp_plan_pair_mask_export.argtypes = [vp, vp, C.c_size_t]
+        L.dasp_plan_pair_mask_export.restype = C.c_longlong
     L.dasp_plan_set_stream_policy.argtypes = [vp, C.c_int]
     if hasattr(L, "dasp_plan_set_tp_exact"):         # (likewise)
         L.dasp_plan_set_tp_exact.argtypes = [vp, C.c_int]
@@ -242,7 +246,7 @@ def check(rc):
 EXPORTS = (
     "dasp_last_error dasp_version dasp_mmio_allinone_f64 dasp_mmio_allinone_f16 dasp_free dasp_csr_save dasp_csr_load dasp_options_default "
     "dasp_plan_create dasp_plan_create_device dasp_plan_download_array dasp_plan_destroy dasp_plan_save dasp_plan_load dasp_plan_order dasp_plan_stats dasp_plan_y_order dasp_plan_x_len dasp_plan_panel_count dasp_plan_panel dasp_plan_panel_range dasp_plan_host_array dasp_plan_upload dasp_plan_tune_placement "
-    "dasp_plan_drop_host dasp_plan_update_values dasp_plan_update_values_host dasp_plan_value_map_slots dasp_plan_csr_fetch_bytes dasp_plan_shared_ids dasp_plan_shared_ids_export dasp_plan_set_stream_policy dasp_plan_set_tp_exact dasp_plan_tp_exact dasp_plan_set_hub_exact dasp_plan_hub_exact dasp_tp_exact_dot_f16 dasp_plan_spmv dasp_plan_spmv_acc dasp_plan_set_f32_vectors dasp_plan_f32_vectors dasp_plan_spmv_f32 dasp_plan_spmv_acc_f32 dasp_plan_spmv_semiring_f32 dasp_plan_time dasp_plan_time_each dasp_plan_time_graph dasp_spmv_all_f64 dasp_spmv_all_f16 dasp_partition_rows "
+    "dasp_plan_drop_host dasp_plan_update_values dasp_plan_update_values_host dasp_plan_value_map_slots dasp_plan_csr_fetch_bytes dasp_plan_shared_ids dasp_plan_shared_ids_export dasp_plan_pair_mask dasp_plan_pair_mask_export dasp_plan_set_stream_policy dasp_plan_set_tp_exact dasp_plan_tp_exact dasp_plan_set_hub_exact dasp_plan_hub_exact dasp_tp_exact_dot_f16 dasp_plan_spmv dasp_plan_spmv_acc dasp_plan_set_f32_vectors dasp_plan_f32_vectors dasp_plan_spmv_f32 dasp_plan_spmv_acc_f32 dasp_plan_spmv_semiring_f32 dasp_plan_time dasp_plan_time_each dasp_plan_time_graph dasp_spmv_all_f64 dasp_spmv_all_f16 dasp_partition_rows "
     "dasp_selftest_mfma dasp_synth_dims dasp_synth_generator dasp_synth_row_lengths dasp_synth_rows "
     "dasp_mg_unique_id dasp_mg_plan_create dasp_mg_destroy dasp_mg_upload dasp_mg_comm_init dasp_mg_set_x dasp_mg_spmv dasp_mg_product dasp_mg_allgather "
     "dasp_mg_wait dasp_mg_get_y dasp_mg_get_y_local dasp_mg_y_local dasp_mg_gathered dasp_mg_x dasp_mg_subplan dasp_mg_info dasp_mg_check dasp_mg_set_fused dasp_mg_set_fake_exchange "

@@ -184,7 +184,13 @@ class Plan:
     def stats(self):
         s = Stats()
         _lib.check(_lib.lib().dasp_plan_stats(self._h, C.byref(s)))
-        return s.as_dict()
+        d = s.as_dict()
+        if hasattr(_lib.lib(), "dasp_plan_pair_mask"):
+            # share of the paired positions whose couples the plan gathers with one 16-byte load (0.0: no shared id plane in use, or DASP_PAIR_GATHER=0)
+            pos, use = C.c_longlong(0), C.c_longlong(0)
+            _lib.check(min(_lib.lib().dasp_plan_pair_mask(self._h, None, C.byref(pos), None, C.byref(use)), 0))
+            d["pair_gather_positions"] = use.value / pos.value if pos.value and use.value else 0.0
+        return d
 
     @property
     def n_panels(self):
@@ -289,6 +295,27 @@ class Plan:
                 _lib.check(n2)
             out.append(a)
         return out[0], out[1].reshape(-1, 4)
+
+    def pair_mask(self):
+        """The pair mask of the shared id plane (include/dasp_amd.h dasp_plan_pair_mask), no GPU needed: a dict with `available`, `words_per_block`,
+        `positions` (of all paired regions), `set_bits` (of the derived mask) and `set_bits_in_use` (of the mask the uploaded plan reads)."""
+        w, pos, sb, use = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        rc = _lib.lib().dasp_plan_pair_mask(self._h, C.byref(w), C.byref(pos), C.byref(sb), C.byref(use))
+        if rc < 0:
+            _lib.check(rc)
+        return {"available": bool(rc), "words_per_block": int(w.value), "positions": int(pos.value), "set_bits": int(sb.value), "set_bits_in_use": int(use.value)}
+
+    def pair_mask_export(self):
+        """The derived pair mask as a uint32 array [medium blocks][words_per_block]: bit i of a block = position i of its paired region."""
+        n = int(_lib.lib().dasp_plan_pair_mask_export(self._h, None, 0))
+        if n < 0:
+            _lib.check(n)
+        a = np.empty(n // 4, np.uint32)
+        n2 = int(_lib.lib().dasp_plan_pair_mask_export(self._h, a.ctypes.data_as(C.c_void_p), a.nbytes))
+        if n2 < 0:
+            _lib.check(n2)
+        w = self.pair_mask()["words_per_block"]
+        return a.reshape(-1, w)
 
     @property
     def value_map_slots(self):

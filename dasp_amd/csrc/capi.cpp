@@ -355,6 +355,41 @@ long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what,
     return rc != DASP_OK ? (long long)rc : need;
 }
 
+int dasp_plan_pair_mask(const dasp_plan_t *plan, int *words_per_block, long long *positions, long long *set_bits, long long *set_bits_in_use)
+{
+    if (!plan) return DASP_ERR_ARG;
+    const Plan &p = plan->impl;
+    if (words_per_block) *words_per_block = 0;
+    if (positions) *positions = 0;
+    if (set_bits) *set_bits = 0;
+    if (set_bits_in_use) *set_bits_in_use = p.dev && p.sh_in_use ? p.pg_set : 0;
+    return guarded("dasp_plan_pair_mask", [&] {
+        SharedIds sh;
+        if (!derive_shared_ids(p, sh)) return 0;
+        if (words_per_block) *words_per_block = sh.pm_words;
+        if (positions) *positions = sh.pair_positions;
+        if (set_bits) *set_bits = sh.pair_set;
+        // not uploaded: what an upload would place NOW (the rules of launch_shape.cpp and the two knobs, read as an upload reads them; no device needed)
+        if (set_bits_in_use && !p.dev)
+            *set_bits_in_use = wants_shared_ids(p) && launch_shape(p, DeviceFacts{}, &sh).shared_ids && pair_gather_knob_allows() ? sh.pair_set : 0;
+        return 1;
+    });
+}
+
+long long dasp_plan_pair_mask_export(const dasp_plan_t *plan, void *dst, size_t bytes)
+{
+    if (!plan) return DASP_ERR_ARG;
+    long long need = 0;
+    const int rc = guarded("dasp_plan_pair_mask_export", [&] {
+        SharedIds sh;
+        if (!derive_shared_ids(plan->impl, sh)) { set_error("the plan has no shared id plane, hence no pair mask (f64 with 16-bit ids, host arrays present, at least one pipelined block)"); return (int)DASP_ERR_STATE; }
+        need = (long long)sh.pair_mask.size() * 4;
+        if (dst && bytes >= (size_t)need && need > 0) std::memcpy(dst, sh.pair_mask.data(), (size_t)need);
+        return (int)DASP_OK;
+    });
+    return rc != DASP_OK ? (long long)rc : need;
+}
+
 int dasp_plan_upload(dasp_plan_t *plan)
 {
     if (!plan) return DASP_ERR_ARG;

@@ -67,9 +67,12 @@ struct DevArgs {
     // (r7; last again) shared id plane of the pipelined blocks' paired regions (plan.hpp struct SharedIds): the ids of rows with identical id lists stored once per block;
     // med_shtab = one 16-byte entry per block {ranks lo, ranks hi, offset into the plane / 16, L}.  Null unless the plan launches dasp_spmv_shared_kernel (DevicePlan::shared_ids), the only kernel that reads them
     const unsigned char *med_shplane; const unsigned *med_shtab;
+    // (r15; last again) the pair mask of the shared plane's paired regions (plan.hpp SharedIds::pair_mask): med_pm_words words per block, bit i = position i of the block's
+    // paired region gathers its couples of adjacent columns with one 16-byte load.  Placed with the plane, read by the same kernel only; all zero under DASP_PAIR_GATHER=0
+    const unsigned *med_pmask; int med_pm_words;
 };
 // the step kernels take the block by value and the device copy is read at fixed offsets: a field is added at the end or not at all
-static_assert(sizeof(DevArgs) == 728 && offsetof(DevArgs, med_shtab) == 720, "DevArgs: the layout the kernels were built against has moved");
+static_assert(sizeof(DevArgs) == 744 && offsetof(DevArgs, med_shtab) == 720 && offsetof(DevArgs, med_pm_words) == 736, "DevArgs: the layout the kernels were built against has moved");
 
 // two-phase form (plan.hpp struct TwoPhase): what its two kernels read.  All device pointers into the plan's arena; xs is the stream phase 1
 // writes and phase 2 reads (one x value per stored element)
@@ -166,6 +169,7 @@ struct Knob { bool set = false; int v = 0; };
 struct ShapeKnobs { Knob long16, seven_waves, share_ids, win_xcd, win1, med_loop, xcd_blocks, wg_rot, win_fold; };      // DASP_LONG16 ... DASP_WIN_FOLD
 ShapeKnobs read_knobs();
 bool y_wt_knob_allows();               // DASP_Y_WT, the tenth: read at every LAUNCH (tools/ywt_ab.py flips it between two launches of one plan); false only for DASP_Y_WT=0
+bool pair_gather_knob_allows();        // DASP_PAIR_GATHER, read at every upload that places a shared id plane; false only for DASP_PAIR_GATHER=0
 bool wants_shared_ids(const Plan &p);  // does an upload of this plan derive the shared id plane at all?  (it streams from HBM, or DASP_SHARE_IDS=1; never under DASP_SHARE_IDS=0)
 bool f16_persistent_set(const Plan &p);      // does the plan take the persistent medium range of uniform f16 blocks?  (the one rule that reads DeviceFacts::f16_resident)
 LaunchShape launch_shape(const Plan &p, const DeviceFacts &dev, const SharedIds *sh);      // sh: the derived plane, null where there is none

@@ -20,6 +20,8 @@ ShapeKnobs read_knobs()
     return k;
 }
 bool y_wt_knob_allows() { const Knob k = knob("DASP_Y_WT"); return !k.set || k.v != 0; }
+// r15: DASP_PAIR_GATHER=0 uploads the pair mask of the shared id plane all zero (upload.cpp) -- the A/B switch of the 16-byte x gathers; it changes nothing launch_shape() reports
+bool pair_gather_knob_allows() { const Knob k = knob("DASP_PAIR_GATHER"); return !k.set || k.v != 0; }
 
 static int ceil_to(int n, int per) { return (n + per - 1) / per; }
 

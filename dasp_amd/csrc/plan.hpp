@@ -364,6 +364,9 @@ struct Plan {
     mutable long long sh_paired_bytes = 0, sh_shared_bytes = 0;
     mutable bool sh_known = false;
     bool sh_in_use = false;
+    // r15: what the last upload put into the pair mask (SharedIds::pair_mask) -- positions of the paired regions and set bits IN USE (0 / 0 without a plane in the arena,
+    // x / 0 under DASP_PAIR_GATHER=0): the `pair_gather_positions` figure of dasp_plan_pair_mask
+    long long pg_positions = 0, pg_set = 0;
     DevicePlan *dev = nullptr;
 
     ~Plan();
@@ -383,6 +386,12 @@ struct SharedIds {
     long long paired_id_bytes = 0;      // what the kernel streams from med_cid8 / med_cid16 for the same positions
     long long shared_bytes = 0;         // plane + table
     int n_pipelined = 0;
+    // r15, the pair mask: pm_words 32-bit words per block (every block, from the plan's longest paired region), bit i of a block = position i of its paired region holds,
+    // in all 16 rows and both couples of lanes (kq 0 | 1) and (kq 2 | 3), adjacent columns c, c + 1 or two pads: the kernel then fetches the couple's x values with ONE
+    // 16-byte gather.  A pad in one lane of a couple clears the bit, as does a pad couple when the matrix has fewer than 2 columns.  Not part of shared_bytes
+    std::vector<uint32_t> pair_mask;
+    int pm_words = 0;
+    long long pair_positions = 0, pair_set = 0;      // positions of all paired regions, and how many of their bits are set
 };
 bool shared_ids_qualify(const Plan &p);                        // f64, 16-bit ids, no windows / panels / two-phase form, host id arrays present
 bool derive_shared_ids(const Plan &p, SharedIds &out);         // false: the plan does not qualify or has no pipelined block (out is empty)

@@ -1,5 +1,6 @@
 // sharedids.cpp -- the shared id plane of a packed plan (plan.hpp struct SharedIds): rows of a pipelined medium block whose packed column-id fields are identical
 // keep ONE copy of them.  Host code without a device: upload.cpp places the result in the arena, capi.cpp answers dasp_plan_shared_ids from it.
+#include <algorithm>
 #include <cstring>
 
 #include "plan.hpp"
@@ -22,6 +23,16 @@ bool derive_shared_ids(const Plan &p, SharedIds &out)
     constexpr int CH = 64, K = 4;                 // f64: elements per chunk, tail entries of a row per step
     const size_t nb = p.med_ptr.size() - 1;
     out.table.assign(4 * nb, 0u);
+    // r15, the pair mask: its words per block follow the plan's longest paired region
+    int max_pair = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        const int nc = p.med_ptr[b + 1] - p.med_ptr[b];
+        const size_t r0 = b * (size_t)kMedRows;
+        const int nt = r0 + 1 < p.irr_ptr.size() ? (p.irr_ptr[r0 + 1] - p.irr_ptr[r0] + K - 1) / K : 0;
+        if (!med_oneshot64(nc, nt)) max_pair = std::max(max_pair, med_npair(nc, nt, 8, p.pair_mode));
+    }
+    out.pm_words = (max_pair + 31) / 32;
+    out.pair_mask.assign((size_t)out.pm_words * nb, 0u);
     const unsigned char *c8 = p.med_cid8.data();
     const unsigned char *c16 = reinterpret_cast<const unsigned char *>(p.med_cid16.data());
     std::vector<const unsigned char *> slot;      // the block's id dwords, 64 per slot (lane = row + 16 kq): narrow batches, then wide pairs
@@ -60,6 +71,27 @@ bool derive_shared_ids(const Plan &p, SharedIds &out)
         out.table[4 * b] = (uint32_t)ranks; out.table[4 * b + 1] = (uint32_t)(ranks >> 32);
         out.table[4 * b + 2] = (uint32_t)(at / 4); out.table[4 * b + 3] = (uint32_t)L;
         out.paired_id_bytes += (long long)slot.size() * 4 * CH;
+        // the pair mask: position i's bit is set when every couple of lanes (row, kq 0 | 1) and (row, kq 2 | 3) of chunk i holds adjacent columns (one chunk, so one base:
+        // offsets differing by one) or two pads -- what lets the kernel fetch both x values with one 16-byte gather.  Two pads read x[0], x[1]: only where x has them
+        for (int i = 0; i < npair; ++i) {
+            const bool narrow = i < n8;
+            const unsigned char *s = narrow ? slot[(size_t)(i / kMedBatch64)] : slot[(size_t)(n8 / kMedBatch64 + (i - n8) / 2)];
+            const unsigned pad = narrow ? 0xFFu : 0xFFFFu;
+            auto field = [&](int lane) -> unsigned {
+                if (narrow) return s[4 * lane + (i & 3)];
+                unsigned short v;
+                std::memcpy(&v, s + 4 * lane + 2 * ((i - n8) & 1), 2);
+                return v;
+            };
+            bool ok = true;
+            for (int r = 0; r < kMedRows && ok; ++r)
+                for (int kq = 0; kq < 4 && ok; kq += 2) {
+                    const unsigned e = field(r + 16 * kq), o = field(r + 16 * (kq + 1));
+                    ok = (e == pad && o == pad) ? p.n >= 2 : (e != pad && o != pad && o == e + 1);
+                }
+            if (ok) { out.pair_mask[b * (size_t)out.pm_words + (size_t)(i >> 5)] |= 1u << (i & 31); ++out.pair_set; }
+        }
+        out.pair_positions += npair;
         ++out.n_pipelined;
         if (at / 4 > 0xFFFFFFFFull) { out = SharedIds(); return false; }      // (64 GiB of ids: the offset no longer fits its word)
     }

@@ -118,7 +118,7 @@ __device__ __forceinline__ DevArgs load_args(const CallArgs &c)
     __builtin_memcpy(&a, w, sizeof a);
 #define DASP_G(f) a.f = ldp(&c.plan->f)
     DASP_G(long_val); DASP_G(long_cid); DASP_G(long_cid16); DASP_G(long_base); DASP_G(piece_c16); DASP_G(piece_ptr); DASP_G(piece_dst); DASP_G(partial); DASP_G(multi_ptr); DASP_G(multi_dst);
-    DASP_G(med_ptr); DASP_G(med_val); DASP_G(med_cid); DASP_G(med_cid16); DASP_G(med_base); DASP_G(med_cid8); DASP_G(med_c8ptr); DASP_G(med_shplane); DASP_G(med_shtab);
+    DASP_G(med_ptr); DASP_G(med_val); DASP_G(med_cid); DASP_G(med_cid16); DASP_G(med_base); DASP_G(med_cid8); DASP_G(med_c8ptr); DASP_G(med_shplane); DASP_G(med_shtab); DASP_G(med_pmask);
     DASP_G(irr_ptr); DASP_G(med_nt); DASP_G(irr_val); DASP_G(irr_cid); DASP_G(med_dst); DASP_G(win_cmin); DASP_G(win_len);
     DASP_G(short_val); DASP_G(short_cid); DASP_G(groups); DASP_G(order);
     DASP_G(rt_val); DASP_G(rt_cid); DASP_G(rt_ptr); DASP_G(rt_start); DASP_G(rt_mask);
@@ -255,7 +255,7 @@ __device__ __forceinline__ void frag_mfma(f32x4 &acc, const Frag<_Float16> &f)
 // lane-linear chunks only (long pieces)
 template <class T, bool NT>
 struct ChunkSrc {
-    static constexpr bool kPairs = false, kQuadIds = false;
+    static constexpr bool kPairs = false, kQuadIds = false, kPairGather = false;
     const T *val; const int *cid; size_t e0; int lane;
     template <bool PAIRED_OK = true> __device__ __forceinline__ void load(Frag<T> &f, int i) const { frag_load<NT>(f, val, cid, e0 + (size_t)i * Tr<T>::CHUNK, lane); }
     template <bool QUAD = false, class XV> __device__ __forceinline__ void gather(Frag<T> &f, int, const XV &x) const { frag_gather(f, x); }
@@ -266,7 +266,7 @@ struct ChunkSrc {
 // Rows are padded to kLongAlign, so a lane's group of the tail is all-in or all-out; lanes beyond it re-read the piece's first group (in bounds) and gather x[0] times 0.
 template <class T, bool NT, bool N16 = false>
 struct PieceSrc {
-    static constexpr bool kPairs = false, kQuadIds = false;
+    static constexpr bool kPairs = false, kQuadIds = false, kPairGather = false;
     static constexpr int VPL = Tr<T>::CHUNK / kWave;
     const T *val; const int *cid; size_t e0; int lane, nfull, tail;
     // N16 (r6, plan.hpp long_cid16): a NARROW piece reads its ids as u16 offsets -- 2 instead of 4 bytes per element -- from its chunks' base columns, a scalar load per
@@ -487,6 +487,95 @@ struct BlockSrc {
         }
         frag_gather(f, x);
     }
+    // (gather4, f64) a step BEHIND the paired region -- a lane-linear chunk (its f.c a raw u16 offset) or a tail step -- as gather() prepares it, except that the value of
+    // a tail entry behind the row's end is left as loaded and its id becomes -2: finish4() zeroes it, once the gathers are issued
+    __device__ __forceinline__ void prep_behind(Frag<T> &f, int i) const
+    {
+        if (i >= nc) f.c = t0 + 4 * (i - nc) + kq < t1 ? f.c : -2;
+        else {
+            const unsigned o = (unsigned)f.c & 0xFFFFu;
+            f.c = o == 0xFFFFu ? -1 : tab<KT>(base, c0 + i) + (int)o;
+        }
+    }
+    // r15 (the shared-id build only): the x gathers of a pipeline batch, two steps at a time.  Lane (row, kq) of step s holds row position 4 s + kq, and a mesh matrix
+    // with several unknowns per node has runs of adjacent columns: where the pair mask (plan.hpp SharedIds::pair_mask) says that in BOTH steps of a pair every couple of
+    // lanes (kq 0 | 1), (kq 2 | 3) wants x[c], x[c + 1] (or two pads), the even lanes fetch the couple's two values of the pair's first step and the odd lanes those of
+    // its second step with ONE 16-byte load each -- one gather instruction where there were two -- and pair_finish() hands the halves across with v_permlane16_swap
+    // (lanes 16 apart).  The same x value reaches the same lane for the same MFMA.  pmask = the block's words of the mask (scalar loads); the test is wave-uniform.
+    // Split in two so that the next batch's streaming loads are issued between the gathers and the first use of what they return, as before.
+    static constexpr bool kPairGather = SH && kQuadIds;
+    const unsigned *pmask;
+    mutable unsigned pw;        // the mask word of the batch gathered next: loaded a batch ahead, so that no gather waits for a scalar load of its own
+    // returns the batch's four mask bits (0 behind the paired region) for finish4()
+    template <class XV> __device__ __forceinline__ unsigned gather4(Frag<T> *f, int i0, const XV &x) const
+    {
+        // vmcnt(0), stated: a batch's ids are the last of its loads (load4), so the gathers wait for all of them anyway.  Behind the wave-uniform branches below, which
+        // leave one or two gathers in flight each, the compiler no longer knows that, and without this it holds back the next batch's id loads (into the registers
+        // of this batch's ids) until the gathers have returned: 0.50 instead of 0.43 ms on HV15R
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        if (i0 + 4 > npair) {                                   // wave-uniform.  Behind the paired region: lane-linear chunks and tail steps, as ever
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { prep_behind(f[u], i0 + u); f[u].b = x.x[f[u].c < 0 ? 0 : f[u].c]; }
+            return 0u;
+        }
+        // the four steps' id fields, cut out of the two raw dwords BEFORE the first branch: both dwords have then arrived on every path, and nothing the branches
+        // leave in flight is taken for a load into the registers the next batch's ids go to
+        const unsigned ra = (unsigned)f[0].c, rb = (unsigned)f[2].c;
+        const bool narrow = i0 < n8;
+        const unsigned pad = narrow ? 0xFFu : 0xFFFFu;
+        const unsigned sh = narrow ? 8u : 16u, sb = narrow ? 16u : 0u;           // narrow: ra == rb holds the four one-byte ids; wide: two u16 each
+        const unsigned o[4] = {ra & pad, (ra >> sh) & pad, (rb >> sb) & pad, (rb >> (sb + sh)) & pad};
+        const unsigned bits = (pw >> (i0 & 31)) & 15u;
+        pair_issue(f[0], f[1], ra, o[0], o[1], pad, sh, 0u, i0, (bits & 3u) == 3u, x);
+        pair_issue(f[2], f[3], rb, o[2], o[3], pad, sh, sb, i0 + 2, (bits & 12u) == 12u, x);
+        const int i1 = i0 + 4;
+        if ((i1 & 31) == 0 && i1 + 4 <= npair) pw = tab<true>(pmask, i1 >> 5);
+        return bits;
+    }
+    __device__ __forceinline__ void finish4(Frag<T> *f, unsigned bits) const
+    {
+        pair_finish(f[0], f[1], (bits & 3u) == 3u);
+        pair_finish(f[2], f[3], (bits & 12u) == 12u);
+    }
+    // steps i (even) and i + 1 inside the paired region: r = the pair's raw id dword, o0 / o1 = the two steps' fields of it, which start at bits s and s + sh
+    template <class XV> __device__ __forceinline__ void pair_issue(Frag<T> &f0, Frag<T> &f1, unsigned r, unsigned o0, unsigned o1, unsigned pad, unsigned sh, unsigned s, int i, bool fast, const XV &x) const
+    {
+        const int b0 = tab<KT>(base, c0 + i), b1 = tab<KT>(base, c0 + i + 1);
+        if (fast) {                                             // wave-uniform
+            const unsigned re = __builtin_amdgcn_permlane16_swap(r, r, false, false)[0];     // odd-kq lanes: the even neighbour's dword; even-kq lanes: their own
+            const bool odd = (kq & 1) != 0;
+            const unsigned oe = (re >> (odd ? s + sh : s)) & pad;                // even lanes: the first step's id; odd lanes: the even neighbour's id of the second step
+            const int ce = oe == pad ? 0 : (odd ? b1 : b0) + (int)oe;            // a couple of pads reads x[0], x[1] (the mask is clear unless x has both) and drops them
+            f64x2 v;
+            __builtin_memcpy(&v, x.x + ce, 16);                 // 8-byte aligned: one global_load_dwordx4
+            f0.b = v[0]; f1.b = v[1];
+        } else {
+            f0.b = x.x[o0 == pad ? 0 : b0 + (int)o0];
+            f1.b = x.x[o1 == pad ? 0 : b1 + (int)o1];
+        }
+        f0.c = o0 == pad ? -1 : 0;                              // the lane's own pads, for pair_finish
+        f1.c = o1 == pad ? -1 : 0;
+    }
+    __device__ __forceinline__ void pair_finish(Frag<T> &f0, Frag<T> &f1, bool fast) const
+    {
+        if (fast) {
+            // even lanes hold {own x of the first step, the odd neighbour's}, odd lanes {the even neighbour's x of the second step, own}: swap the even lanes' upper
+            // double with the odd lanes' lower one -- v_permlane16_swap exchanges the odd rows of its first operand with the even rows of its second
+            unsigned lo[2], hi[2];
+            __builtin_memcpy(lo, &f0.b, 8); __builtin_memcpy(hi, &f1.b, 8);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const auto t = __builtin_amdgcn_permlane16_swap(lo[h], hi[h], false, false);
+                lo[h] = t[0]; hi[h] = t[1];
+            }
+            __builtin_memcpy(&f0.b, lo, 8); __builtin_memcpy(&f1.b, hi, 8);
+        }
+        // (no value is touched between a batch's loads and this point: a value changed under one of the wave-uniform branches of the gathers would have to be
+        // copied under the other, and the copy waits for everything in flight)
+        f0.a = f0.c == -2 ? 0.0 : f0.a; f1.a = f1.c == -2 ? 0.0 : f1.a;
+        f0.b = f0.c < 0 ? 0.0 : f0.b;
+        f1.b = f1.c < 0 ? 0.0 : f1.b;
+    }
 };
 
 // the loads of the N consecutive steps from i0: pair loads when the source stores pairs and the whole batch lies in its paired
@@ -558,9 +647,15 @@ struct FinishDispatch {
     {
         if (rem == R) {
             Frag<T> r[R > 0 ? R : 1];
+            if constexpr (SRC::kPairGather && U == 4) {         // (r15: the batch's gathers in two halves around the loads, BlockSrc::gather4)
+                const unsigned pg = src.gather4(cur, ibase, x);
+                load_steps<R>(src, r, i);
+                src.finish4(cur, pg);
+            } else {
 #pragma unroll
-            for (int u = 0; u < U; ++u) src.template gather<true>(cur[u], ibase + u, x);
-            load_steps<R>(src, r, i);
+                for (int u = 0; u < U; ++u) src.template gather<true>(cur[u], ibase + u, x);
+                load_steps<R>(src, r, i);
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) frag_mfma(acc, cur[u]);
 #pragma unroll
@@ -585,9 +680,15 @@ __device__ __forceinline__ void run_stream(ACC &acc, const SRC &src, int N, cons
     int i = U;
     for (int it = 1; it < nfull; ++it, i += U) {
         Frag<T> nxt[U];
+        if constexpr (SRC::kPairGather && U == 4) {
+            const unsigned pg = src.gather4(cur, i - U, x);
+            load_steps<U>(src, nxt, i);
+            src.finish4(cur, pg);
+        } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) src.template gather<true>(cur[u], i - U + u, x);
-        load_steps<U>(src, nxt, i);
+            for (int u = 0; u < U; ++u) src.template gather<true>(cur[u], i - U + u, x);
+            load_steps<U>(src, nxt, i);
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) frag_mfma(acc, cur[u]);
 #pragma unroll
@@ -681,6 +782,8 @@ __device__ __forceinline__ void medium_block(const DevArgs &a, int b, int lane, 
         src.sh4l = 4u * L; src.shlane4 = 4u * ((unsigned)kq * L + ((rw >> (4u * (unsigned)(row & 7))) & 15u));
         src.shn = (gbyte_p)a.med_shplane + (size_t)e[2] * 16;
         src.shw = src.shn - (size_t)((unsigned)src.n8 * src.sh4l);
+        src.pmask = a.med_pmask + (size_t)b * (size_t)a.med_pm_words;
+        src.pw = tab<true>(src.pmask, 0);
     }
     src.ival = static_cast<const T *>(a.irr_val); src.icid = a.irr_cid; src.t0 = t0; src.t1 = t1; src.kq = kq;
     // (the windowed f16 kernels, held to 64 registers, keep blocks of up to 2 steps in one shot: 4 spill there; windowed plans store no pairs, so their layout does not depend on it)

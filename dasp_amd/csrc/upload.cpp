@@ -304,8 +304,14 @@ static int upload_row_forms(Plan &p, DevicePlan *d)
         carry_plane = have && launch_shape(p, DeviceFacts{}, &sh).shared_ids;
     }
     p.sh_in_use = carry_plane;
-    size_t o_shp = 0, o_sht = 0;
+    size_t o_shp = 0, o_sht = 0, o_pm = 0;
     if (carry_plane) { o_shp = add(sh.plane.data(), sh.plane.size() * 4); o_sht = add(sh.table.data(), sh.table.size() * 4); }
+    // r15: the pair mask travels with the plane.  DASP_PAIR_GATHER=0 (read here, like DASP_SHARE_IDS) uploads it all zero: the same kernel, every couple on two 8-byte gathers
+    if (carry_plane) {
+        if (!pair_gather_knob_allows()) { std::fill(sh.pair_mask.begin(), sh.pair_mask.end(), 0u); sh.pair_set = 0; }
+        o_pm = add(sh.pair_mask.data(), sh.pair_mask.size() * 4);
+    }
+    p.pg_positions = carry_plane ? sh.pair_positions : 0; p.pg_set = carry_plane ? sh.pair_set : 0;
 
     HIP_TRY(hipMalloc(&d->arena, total));
     d->arena_bytes = total;
@@ -334,6 +340,7 @@ static int upload_row_forms(Plan &p, DevicePlan *d)
     a.med_cid16 = (const unsigned short *)(base + o_mc16); a.med_base = (const int *)(base + o_mb);
     a.med_cid8 = (const unsigned char *)(base + o_mc8); a.med_c8ptr = (const int *)(base + o_c8p);
     a.med_shplane = carry_plane ? (const unsigned char *)(base + o_shp) : nullptr; a.med_shtab = carry_plane ? (const unsigned *)(base + o_sht) : nullptr;
+    a.med_pmask = carry_plane ? (const unsigned *)(base + o_pm) : nullptr; a.med_pm_words = carry_plane ? sh.pm_words : 0;
     a.med_dst = (const int *)(base + o_mdst); a.win_cmin = (const int *)(base + o_wc); a.win_len = (const int *)(base + o_wl);
     a.n_windows = (int)p.win_len.size(); a.blocks_per_win = p.windowed ? p.row_window / kMedRows : 0;
     a.win_hybrid = p.win_hybrid ? 1 : 0; a.win_rel16 = p.win_rel16 ? 1 : 0; a.pair_mode = p.pair_mode;
@@ -387,7 +394,7 @@ static void rebase_args(DevArgs &a, const char *from, const char *to, size_t byt
     mv(a.med_ptr); mv(a.med_val); mv(a.med_cid); mv(a.med_cid16); mv(a.med_base); mv(a.med_cid8); mv(a.med_c8ptr);
     mv(a.irr_ptr); mv(a.med_nt); mv(a.irr_val); mv(a.irr_cid); mv(a.med_dst); mv(a.win_cmin); mv(a.win_len);
     mv(a.short_val); mv(a.short_cid); mv(a.groups); mv(a.order);
-    mv(a.med_shplane); mv(a.med_shtab);
+    mv(a.med_shplane); mv(a.med_shtab); mv(a.med_pmask);
 }
 
 int tune_placement(Plan &p, int trials, const void *dX, void *dY, double *ms_first, double *ms_kept)

@@ -385,6 +385,19 @@ int dasp_plan_shared_ids(const dasp_plan_t *plan, long long *paired_id_bytes, lo
  * units of 16 bytes; its number of lists L; all zero for a block that is not pipelined).  Returns the size in bytes (the copy is made when dst holds at
  * least that much), < 0 on error. */
 long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what, void *dst, size_t bytes);
+/* The pair mask of a plan that has a shared id plane: one bit per position of every pipelined block's paired region, set when all 16 rows of that chunk hold, in
+ * both couples of neighbouring lanes (row positions 4 step + 0 | 1 and 4 step + 2 | 3), two adjacent columns c, c + 1 or two pads (pads count only when the matrix
+ * has at least 2 columns).  The kernel that reads the plane fetches such couples' x values with ONE 16-byte gather; the same values reach the same lanes, so y is
+ * bit for bit the same.  DASP_PAIR_GATHER=0, read at upload, places an all-zero mask: the same kernel, every couple on two 8-byte gathers.
+ * dasp_plan_pair_mask answers without a GPU: *words_per_block = 32-bit words of every medium block (bit i of a block = bit i % 32 of its word i / 32; from the plan's
+ * longest paired region), *positions = positions of all paired regions, *set_bits = set bits of the derived mask, *set_bits_in_use = set bits of the mask the
+ * uploaded plan reads (0 when it carries no plane or was uploaded under DASP_PAIR_GATHER=0); for a plan that is not uploaded, of the mask an upload would place
+ * now (the same rules and knobs, read at the call).  Returns 1 when the plan has a mask, 0 when it has none (everything 0), < 0 on error.  Any out pointer may
+ * be null. */
+int dasp_plan_pair_mask(const dasp_plan_t *plan, int *words_per_block, long long *positions, long long *set_bits, long long *set_bits_in_use);
+/* copy out the derived mask (words_per_block words for every medium block, in block order).  Returns the size in bytes (the copy is made when dst holds at least
+ * that much), < 0 on error. */
+long long dasp_plan_pair_mask_export(const dasp_plan_t *plan, void *dst, size_t bytes);
 
 /* switch the cache policy of an uploaded plan (values as dasp_options_t::stream_policy); no re-upload */
 int dasp_plan_set_stream_policy(dasp_plan_t *plan, int policy);

@@ -33,6 +33,36 @@ template <class T, int P> void run(const T *x, size_t n, double *out)
 {
     hipLaunchKernelGGL((g<T, P>), dim3(4096), dim3(256), 0, 0, x, n, out, 64);
 }
+// r15: ONE 16-byte gather of two adjacent doubles (x[c], x[c + 1] from an 8-byte-aligned pointer: one global_load_dwordx4) against the TWO 8-byte gathers it
+// replaces (W = 8: x[c] and x[c + 1] as two loads).  pattern P: the element (a pair of doubles) lane l reads
+//  0: quads share an element, quads 16 B apart      1: quads share an element, quads 1 KB apart      2: the four lanes of a quad on two elements 40 B apart, quads 1 KB apart
+// SHIFT = the byte offset of every element: 0 (16-byte aligned), 8 (8- but not 16-byte aligned), 120 (the element straddles a 128-byte line)
+template <int W, int P, int SHIFT>
+__global__ void g2(const double *x, size_t n, double *out, int iters, int one)
+{
+    const int l = threadIdx.x & 63;
+    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int q = l >> 2, r = l & 3;
+    const size_t off = (P == 0 ? (size_t)q * 2 : P == 1 ? (size_t)q * 128 : (size_t)q * 128 + 5 * (r >> 1)) + SHIFT / 8;
+    double s = 0;
+    for (int it = 0; it < iters; ++it) {
+        const size_t base = ((wave * 131 + (size_t)it * 7919) * 4096) % (n - 65536);
+        const double *p = x + base + off;
+        if (W == 16) {
+            double v[2];
+            __builtin_memcpy(v, p, 16);
+            s += v[0] + v[1];
+        } else {
+            const double a = p[0], b = p[one];          // (one = 1, a kernel argument: the compiler cannot merge the two loads)
+            s += a + b;
+        }
+    }
+    if (s == 12345.678) out[0] = s;
+}
+template <int W, int P, int SHIFT> void run2(const double *x, size_t n, double *out)
+{
+    hipLaunchKernelGGL((g2<W, P, SHIFT>), dim3(4096), dim3(256), 0, 0, x, n, out, 64, 1);
+}
 int main()
 {
     const size_t bytes = (size_t)64 << 20;
@@ -43,6 +73,8 @@ int main()
                run<T, 3>((const T *)buf, bytes / sizeof(T), out); run<T, 4>((const T *)buf, bytes / sizeof(T), out); run<T, 5>((const T *)buf, bytes / sizeof(T), out); \
                run<T, 6>((const T *)buf, bytes / sizeof(T), out); run<T, 7>((const T *)buf, bytes / sizeof(T), out);
     ALL(_Float16) ALL(float) ALL(double)
+#define ALL2(W, S) run2<W, 0, S>((const double *)buf, bytes / 8, out); run2<W, 1, S>((const double *)buf, bytes / 8, out); run2<W, 2, S>((const double *)buf, bytes / 8, out);
+    ALL2(16, 0) ALL2(16, 8) ALL2(16, 120) ALL2(8, 0) ALL2(8, 8) ALL2(8, 120)
     (void)hipDeviceSynchronize();
     std::printf("done\n");
     return 0;
