@@ -519,11 +519,6 @@ __global__ void k_panel_scatter(const int *rp, const int *ci, const T *val, int 
 
 // splits the device CSR `d` of plan `p` into P column ranges [bnd[k], bnd[k + 1]).  rpP_host[k] = the panel's row pointer (host copy);
 // out[k] = its device CSR (columns already remapped).  The device arrays are owned by `keep` (freed with it).
-int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
-                        std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep)
-{
-    return devpack_panel_split_masked(p, d, bnd, P, rpP_host, out, keep, nullptr);
-}
 int devpack_panel_split_masked(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
                                std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep, const unsigned char *mask)
 {

@@ -8,14 +8,19 @@
 //   reference_geometry                                      the CUDA reference's padded sizes of the same input
 //   LapTimer, Build<T>                                      the DASP_VERBOSE stage timer; the state the stages of one build hand on
 //   validate_csr, sort_columns                              entry work of a whole plan
-//   lcb_counters, hub_rows, hybrid_then_tp, hybrid_then_tp_device, hybrid_then_tp_fetched     the two-phase / hybrid form from a host, a device, a fetched device CSR
+//   lcb_counters, slot_table, hub_rows, FetchedCsr<T> / fetch_device_csr                     what the hybrid and the column panels share: the hub rows' counters, the slot table, a device CSR copied to the host
+//   hybrid_then_tp, hybrid_then_tp_device, hybrid_then_tp_fetched                            the two-phase / hybrid form from a host, a device, a fetched device CSR
 //   the stages of the DASP form, in the order run_stages calls them:
 //     classify_rows, sort_medium_by_length, measure_reference, assign_slots (+ slabs_pay),
 //     decide_windows (+ default_row_window, order_in_windows, scan_window_spans, fit_windows, hybrid_windows, windows_pay),
 //     medium_rows_as_pieces, pack_long, split_medium_chunks, pack_medium, pack_short, fill_stats, finish
 //   build_dasp                                              the DASP form for a metadata-only plan or one column panel
 //   build_form                                              which form a whole plan takes: two-phase / hybrid, column panels, or the plain DASP form
-//   decide_panels, build_panels                             the column panels
+//   decide_panels                                           the column panels' rule
+//   RowTiles, cut_row_tiles, PanelBuild<T>                  a panel's row tiles; the state the stages of one panel build hand on
+//   the stages of the column panels, in the order build_panels calls them:
+//     panel_bounds, slot_table, hub_rows_leave_panels, row_tile_bound, split_host / split_device,
+//     build_panel_plans (+ make_panel_plan), collect_panels, sum_panel_counters (+ lcb_counters), upload_parent
 //   build_plan                                              the entry point (plan.hpp)
 #include "plan.hpp"
 
@@ -581,21 +586,59 @@ template <class T> static int sort_columns(Build<T> &bld, SortedCsr<T> &sorted)
 
 // the hybrid (r6): hub rows -- the rule of the column-blocked long rows, decide_long_cb -- leave the two-phase streams for
 // Plan::lcb (x staged in LDS per column block, no atomics on one LDS word per hub row); everything else stays two-phase
-static void lcb_counters(Plan &p)
+// the hub rows' counters (Plan::lcb) added to the plan's: their streams (values + local columns) and every unit's slice of x (xlen columns in all).
+// panels_stored: nullptr for the hybrid, whose partials live in LDS.  The parent of column panels passes the elements its panels store: it also counts the
+// hub rows' partial planes, written and read, and takes rate_fill0 again over the panels' elements and the hub rows' together
+static void lcb_counters(Plan &p, long long xlen, const long long *panels_stored)
 {
     const LongCB &L = p.lcb;
     dasp_stats_t &s = p.stats;
+    const long long vb = p.geo.vbytes;
     s.lcb_rows = L.n_rows(); s.lcb_elems = (long long)L.elems; s.lcb_col_block = L.cb; s.lcb_units = L.n_units();
     s.n_workgroups += L.n_units() + ceil_div(L.n_rows(), kWavesPerWG);
-    s.data_X += (long long)L.elems * (p.geo.vbytes + 2) + (long long)L.n_units() * (long long)std::min(L.cb, p.n) * p.geo.vbytes;
+    s.data_X += (long long)L.elems * (vb + 2) + (long long)L.n_units() * std::min<long long>(L.cb, xlen) * vb;
+    if (!panels_stored) return;
+    s.data_X += 2ll * L.n_cb * L.n_rows() * 8;
+    s.rate_fill0 = p.nnz > 0 ? (double)(*panels_stored + (long long)L.elems - p.nnz) / p.nnz : 0.0;
+}
+// slot_of_row[row] = the row's slot in order_rid; left empty for a plan whose y is in row order
+static void slot_table(const Plan &p, std::vector<int> &slot_of_row)
+{
+    if (p.opt.y_order == DASP_Y_NATURAL) return;
+    const int m = p.m;
+    slot_of_row.resize((size_t)m);
+    for (int i = 0; i < m; ++i) slot_of_row[(size_t)p.order[(size_t)i]] = i;
 }
 static bool hub_rows(Plan &p, const int *rp, std::vector<unsigned char> &in_lcb, std::vector<int> &slot_of_row)
 {
-    const int m = p.m;
     p.lcb = LongCB{};
     if (decide_long_cb(p, rp, 2, in_lcb, 4, 128) <= 0) return false;
-    if (p.opt.y_order != DASP_Y_NATURAL) { slot_of_row.resize((size_t)m); for (int i = 0; i < m; ++i) slot_of_row[(size_t)p.order[(size_t)i]] = i; }
+    slot_table(p, slot_of_row);
     return true;
+}
+// a device CSR copied to the host (the fallback of the device packers: DASP_DEVPACK_FORMS=0, or no room for their scratch): the column ids and values, and for
+// a column-sorted device CSR under a value map its map entries too (else the host's own index + 1 is the map).  Plan::csr_fetch_bytes counts what crossed;
+// p.map_src points into `out` from here on, so `out` outlives the packing and the top-level build resets map_src (build_form)
+template <class T> struct FetchedCsr {
+    raw_vector<int> ci;
+    raw_vector<T> val;
+    raw_vector<uint32_t> src;
+    bool on = false;                 // fetch_device_csr succeeded: ci and val are the matrix
+};
+template <class T> static int fetch_device_csr(Plan &p, const DevCsr &dev, FetchedCsr<T> &out)
+{
+    const size_t nnz = (size_t)p.nnz;
+    out.ci.resize(nnz); out.val.resize(nnz);
+    if (int rc = devpack_fetch_csr(p, dev, out.ci.data(), out.val.data())) return rc;
+    p.csr_fetch_bytes += (long long)p.nnz * (4 + (long long)sizeof(T));
+    if (p.value_map && dev.src) {
+        out.src.resize(nnz);
+        if (int rc = devpack_fetch_csr(p, DevCsr{dev.rp, reinterpret_cast<const int *>(dev.src), nullptr}, reinterpret_cast<int *>(out.src.data()), nullptr)) return rc;
+        p.csr_fetch_bytes += (long long)p.nnz * 4;
+        p.map_src = out.src.data();
+    }
+    out.on = true;
+    return DASP_OK;
 }
 template <class T> static int hybrid_then_tp(Build<T> &bld, const int *hci, const T *hval)
 {
@@ -611,7 +654,7 @@ template <class T> static int hybrid_then_tp(Build<T> &bld, const int *hci, cons
     }
     const int rc_t = build_two_phase(p, rp, hci, hval, in_lcb.empty() ? nullptr : in_lcb.data());
     if (rc_t != DASP_OK) { p.lcb = LongCB{}; return rc_t; }
-    if (!in_lcb.empty()) lcb_counters(p);
+    if (!in_lcb.empty()) lcb_counters(p, p.n, nullptr);
     return DASP_OK;
 }
 // the same from a device CSR (r8): the hub rows' pieces and the tiles are counted, ranked and written by devpack.hip, the rules and tables are the host's
@@ -634,7 +677,7 @@ template <class T> static int hybrid_then_tp_device(Build<T> &bld)
     int rc_t = build_two_phase_device(p, rp, *dev, in_lcb.empty() ? nullptr : in_lcb.data(), tiles, off2, off1);
     bld.lap("two-phase tiles (device)");
     if (rc_t == DASP_OK) {
-        if (!in_lcb.empty()) lcb_counters(p);
+        if (!in_lcb.empty()) lcb_counters(p, p.n, nullptr);
         rc_t = devpack_finish_two_phase(p, *dev, tiles, off2, off1, pieces);
         bld.lap("two-phase streams (device)");
     }
@@ -646,21 +689,10 @@ template <class T> static int hybrid_then_tp_device(Build<T> &bld)
 template <class T> static int hybrid_then_tp_fetched(Build<T> &bld)
 {
     Plan &p = bld.p;
-    const DevCsr *dev = bld.dev;
-    const int nnz = bld.nnz;
-    raw_vector<int> hci((size_t)nnz);
-    raw_vector<T> hval((size_t)nnz);
-    raw_vector<uint32_t> hsrc;
-    if (int rc = devpack_fetch_csr(p, *dev, hci.data(), hval.data())) return rc;
-    p.csr_fetch_bytes += (long long)nnz * (4 + (long long)sizeof(T));
-    if (p.value_map && dev->src) {      // a column-sorted device CSR: its map entries travel too (else the host's own index + 1 is the map)
-        hsrc.resize((size_t)nnz);
-        if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(hsrc.data()), nullptr)) return rc;
-        p.csr_fetch_bytes += (long long)nnz * 4;
-        p.map_src = hsrc.data();
-    }
-    const int rc2 = hybrid_then_tp(bld, hci.data(), hval.data());
-    p.map_src = nullptr;      // (hsrc ends here)
+    FetchedCsr<T> host;
+    if (int rc = fetch_device_csr(p, *bld.dev, host)) return rc;
+    const int rc2 = hybrid_then_tp(bld, host.ci.data(), host.val.data());
+    p.map_src = nullptr;      // (host.src ends here)
     bld.lap("two-phase streams (device CSR fetched)");
     return rc2;
 }
@@ -1937,119 +1969,158 @@ static int decide_panels(const Plan &p, const CsrProbe &probe, int *scattered)
     return (int)std::max<long long>(2, std::min<long long>(std::min(by_x, by_len), 8));
 }
 
-template <class T>
-static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int P, const DevCsr *dev)
-{
-    const DevCsr *const dev_in = dev;       // (the fallback of the hub rows' device packer fetches the CSR and splits it on the host: see long_cb below)
-    LapTimer lap("[dasp panels] %-26s %.3f s\n");
-    // whole-matrix classification: order_rid and the reference's counters are those of the unsplit matrix (row lengths only)
-    if (int rc = build_dasp<T>(p, rp, ci, val, nullptr, true)) return rc;
-    lap("whole-matrix meta");
-    const int m = p.m;
-    const int threads = resolve_threads(p.opt.host_threads);
-    Remap remap;
-    remap.n_parts = p.opt.n_parts; remap.stride = p.opt.part_stride; remap.b = p.part_bounds.data();
-    const long long xlen = p.opt.n_parts > 0 ? (long long)p.opt.n_parts * p.opt.part_stride : (long long)p.n;
-    std::vector<int> bnd((size_t)P + 1);
-    for (int k = 0; k <= P; ++k) bnd[k] = (int)std::min<long long>(xlen, ((xlen * k / P + 63) / 64) * 64);   // whole 128-byte lines
-    bnd[0] = 0; bnd[P] = (int)xlen;
-    auto panel_of = [&](int c) { return (int)(std::upper_bound(bnd.begin() + 1, bnd.end(), c) - bnd.begin()) - 1; };
+namespace {
+// row tiles (opt.row_tile_max, Plan::rt_*): a panel keeps its rows of <= the tile bound nonzeros in the parent's output order.  The tiles' tables, their elements
+// (host split only: val, cid, map), at[row] = the row's first element in the tiles' arrays (-1: the row stays with the panel's own plan), cnt = the elements
+struct RowTiles { std::vector<int> ptr; std::vector<uint16_t> start; std::vector<uint64_t> mask; raw_vector<char> val; raw_vector<int> cid; std::vector<int> at; size_t cnt = 0; std::vector<uint32_t> map; };
 
-    // split the CSR by column range: count, prefix, scatter (row-parallel; the rows' internal order is kept)
-    std::vector<std::vector<int>> rpP((size_t)P);
-    std::vector<raw_vector<int>> ciP((size_t)P);
-    std::vector<raw_vector<T>> valP((size_t)P);
-    std::vector<raw_vector<uint32_t>> srcP((size_t)P);   // value map: the caller's nonzero (+1) at every position of panel k's sub-CSR
-    std::vector<DevCsr> devP;                          // device CSR: the same split by two kernels (devpack.hip), sub-matrices stay on the GPU
-    std::vector<std::shared_ptr<void>> dev_keep;
-    std::vector<DevRowTiles> rt_dev((size_t)P);        // device path: the tiles' elements, moved into the panel plan's arena once it exists
-    std::vector<std::vector<std::shared_ptr<void>>> rt_keep((size_t)P);
-    const bool natural = p.opt.y_order == DASP_Y_NATURAL;
-    std::vector<int> slot_of_row;
-    if (!natural) { slot_of_row.resize((size_t)m); for (int i = 0; i < m; ++i) slot_of_row[p.order[i]] = i; }
-    lap("slot table");
-    // column-blocked long rows (opt.long_cb, plan.hpp struct LongCB): the hub rows leave the panels -- in_lcb[row] -- and get their own LDS-staged kernel
-    std::vector<unsigned char> in_lcb;
-    raw_vector<int> lcb_ci;
-    raw_vector<T> lcb_val;
-    raw_vector<uint32_t> lcb_src;
-    p.lcb = LongCB{};
-    DevTiles lcb_pieces;      // device path: the hub rows' sorted pieces, from the count here to the fill into the parent's arena (devpack_finish_panels_lcb)
-    if (decide_long_cb(p, rp, P, in_lcb) > 0) {
-        int rc_lcb = kDevNoScratch;
-        if (dev && devpack_forms_enabled()) rc_lcb = build_long_cb_device(p, rp, *dev, in_lcb, natural ? nullptr : slot_of_row.data(), lcb_pieces);
-        if (dev && rc_lcb == kDevNoScratch) {      // the fallback (DASP_DEVPACK_FORMS=0, or no room for the packer's scratch): fetch the nonzeros once, then the host packer and the host split below
-            lcb_ci.resize((size_t)p.nnz); lcb_val.resize((size_t)p.nnz);
-            if (int rc = devpack_fetch_csr(p, *dev, lcb_ci.data(), lcb_val.data())) return rc;
-            p.csr_fetch_bytes += (long long)p.nnz * (4 + (long long)sizeof(T));
-            if (p.value_map && dev->src) {      // (see the two-phase fetch in hybrid_then_tp_fetched)
-                lcb_src.resize((size_t)p.nnz);
-                if (int rc = devpack_fetch_csr(p, DevCsr{dev->rp, reinterpret_cast<const int *>(dev->src), nullptr}, reinterpret_cast<int *>(lcb_src.data()), nullptr)) return rc;
-                p.csr_fetch_bytes += (long long)p.nnz * 4;
-                p.map_src = lcb_src.data();
-            }
-            ci = lcb_ci.data(); val = lcb_val.data(); dev = nullptr;
+// from a panel's row LENGTHS in len[1 .. m] (len[i + 1] = row i): the tables of its tiles of rows of <= rt_max nonzeros, in the output order (order[slot] = row;
+// nullptr: row order); the rows taken get length 0 in len
+void cut_row_tiles(RowTiles &R, int rt_max, const int *order, int m, int *len)
+{
+    const int tiles = ceil_div(m, kRowTile);
+    R.ptr.assign((size_t)tiles + 1, 0); R.start.assign((size_t)tiles * kRowTile, 0); R.mask.assign((size_t)tiles, 0); R.at.assign((size_t)m, -1);
+    long long run = 0;
+    for (int t = 0; t < tiles; ++t) {
+        int in_tile = 0;
+        for (int i = 0; i < kRowTile; ++i) {
+            const int j = t * kRowTile + i;
+            R.start[(size_t)j] = (uint16_t)in_tile;
+            if (j >= m) continue;
+            const int r = order ? order[(size_t)j] : j, L = len[(size_t)r + 1];
+            if (L > rt_max) continue;
+            R.mask[(size_t)t] |= uint64_t(1) << i;
+            if (L > 0) { R.at[(size_t)r] = (int)(run + in_tile); in_tile += L; len[(size_t)r + 1] = 0; }
         }
-        if (!dev) rc_lcb = build_long_cb(p, rp, ci, val, in_lcb, natural ? nullptr : slot_of_row.data());
-        if (rc_lcb == 1) in_lcb.clear();          // (a piece too long for the kernel's LDS slice: the rows stay in the panels)
-        else if (rc_lcb) return rc_lcb;
-        lap("long rows by column block");
+        run += in_tile;
+        R.ptr[(size_t)t + 1] = (int)run;
     }
-    const bool lcb_on = !in_lcb.empty();
-    // row tiles (opt.row_tile_max, Plan::rt_*): panel k keeps its rows of <= rt_max nonzeros in the parent's output order; rt[k] holds their
-    // tables, rt_at[k][row] = the row's first element in the tiles' arrays (-1: the row stays with the panel's own plan)
+    R.cnt = (size_t)run;
+}
+
+// ---- the state of one build of column panels: what its stages (build_panels) read and hand on, in the style of Build<T>.  Every member names ONE quantity; the
+// comment says which stage writes it
+template <class T> struct PanelBuild {
+    // inputs, fixed at construction
+    Plan &p;
+    const int *const rp;
+    const int P, m, threads;
+    const long long xlen;                  // columns of x: n, or the padded length of a partitioned x
+    const bool natural;                    // y in row order
+    Remap remap;
+    const int *const ci_in;                // the caller's CSR: host arrays, or ...
+    const T *const val_in;
+    const DevCsr *const dev_in;            // ... a device CSR (then ci_in and val_in are not read)
+    LapTimer lap{"[dasp panels] %-26s %.3f s\n"};
+
+    // hub_rows_leave_panels, and no other stage: the fallback of the hub rows' device packer copies the caller's device CSR to the host; from then on the
+    // build reads the copy like a host CSR (ci, val, dev below), and only the parent's upload remembers dev_in
+    FetchedCsr<T> fetched;
+    // the CSR the stages read: exactly one of host ci / val and a device CSR
+    const int *ci() const { return fetched.on ? fetched.ci.data() : ci_in; }
+    const T *val() const { return fetched.on ? fetched.val.data() : val_in; }
+    const DevCsr *dev() const { return fetched.on ? nullptr : dev_in; }
+
+    std::vector<int> bnd;                  // panel_bounds: panel k holds the columns [bnd[k], bnd[k + 1])
+    std::vector<int> slot_of_row;          // slot_table (empty when natural)
+    // hub_rows_leave_panels: column-blocked long rows (opt.long_cb, plan.hpp struct LongCB): in_lcb[row] = the row leaves the panels for Plan::lcb; empty = none does
+    std::vector<unsigned char> in_lcb;
+    DevTiles lcb_pieces;                   // hub_rows_leave_panels, device packer: the hub rows' sorted pieces, kept from the count to the fill into the parent's arena (upload_parent)
+    int rt_max = 0;                        // row_tile_bound: the longest row a tile takes (0: no tiles)
+    // split_host / split_device: panel k's sub-CSR -- its row pointer (host), then host ids, values and (value map) the caller's nonzero + 1 at every position, or a
+    // device CSR owned by dev_keep -- and its row tiles.  make_panel_plan frees the host arrays and moves the tiles' tables into the panel's plan
+    std::vector<std::vector<int>> rpP;
+    std::vector<raw_vector<int>> ciP;
+    std::vector<raw_vector<T>> valP;
+    std::vector<raw_vector<uint32_t>> srcP;
+    std::vector<DevCsr> devP;
+    std::vector<std::shared_ptr<void>> dev_keep;
+    std::vector<RowTiles> rt;
+    // make_panel_plan, device path: the tiles' elements, moved into the panel plan's arena once it exists
+    std::vector<DevRowTiles> rt_dev;
+    std::vector<std::vector<std::shared_ptr<void>>> rt_keep;
+    // build_panel_plans: per panel its plan (null: an empty panel), its status and its error text
+    std::vector<std::unique_ptr<dasp_plan>> built;
+    std::vector<int> rcs;
+    std::vector<std::string> errs;
+
+    PanelBuild(Plan &p_, const int *rp_, const int *ci_, const T *val_, int P_, const DevCsr *dev_)
+        : p(p_), rp(rp_), P(P_), m(p_.m), threads(resolve_threads(p_.opt.host_threads)),
+          xlen(p_.opt.n_parts > 0 ? (long long)p_.opt.n_parts * p_.opt.part_stride : (long long)p_.n), natural(p_.opt.y_order == DASP_Y_NATURAL),
+          ci_in(ci_), val_in(val_), dev_in(dev_), rpP((size_t)P_), ciP((size_t)P_), valP((size_t)P_), srcP((size_t)P_), rt((size_t)P_), rt_dev((size_t)P_), rt_keep((size_t)P_),
+          built((size_t)P_), rcs((size_t)P_, DASP_OK), errs((size_t)P_)
+    {
+        remap.n_parts = p.opt.n_parts; remap.stride = p.opt.part_stride; remap.b = p.part_bounds.data();
+    }
+    PanelBuild(const PanelBuild &) = delete;
+    PanelBuild &operator=(const PanelBuild &) = delete;
+    bool lcb_on() const { return !in_lcb.empty(); }
+    const int *order() const { return natural ? nullptr : p.order.data(); }      // what cut_row_tiles takes
+    const int *slots() const { return natural ? nullptr : slot_of_row.data(); }  // what the hub rows' packers take
+};
+inline int panel_of(const std::vector<int> &bnd, int c) { return (int)(std::upper_bound(bnd.begin() + 1, bnd.end(), c) - bnd.begin()) - 1; }
+}  // namespace
+
+// ---- panel bounds: equal shares of x, cut at whole 128-byte lines (64 columns)
+template <class T> static void panel_bounds(PanelBuild<T> &st)
+{
+    const int P = st.P;
+    const long long xlen = st.xlen;
+    st.bnd.resize((size_t)P + 1);
+    for (int k = 0; k <= P; ++k) st.bnd[k] = (int)std::min<long long>(xlen, ((xlen * k / P + 63) / 64) * 64);
+    st.bnd[0] = 0; st.bnd[P] = (int)xlen;
+}
+
+// ---- the hub rows leave the panels for their own LDS-staged kernel (Plan::lcb) where decide_long_cb says so: packed on the device from a device CSR, else -- a
+// host CSR, or the device packer's fallback (DASP_DEVPACK_FORMS=0, or no room for its scratch), which fetches the nonzeros once -- by the host packer; the host split follows
+template <class T> static int hub_rows_leave_panels(PanelBuild<T> &st)
+{
+    Plan &p = st.p;
+    p.lcb = LongCB{};
+    if (decide_long_cb(p, st.rp, st.P, st.in_lcb) <= 0) return DASP_OK;
+    int rc_lcb = kDevNoScratch;
+    if (st.dev() && devpack_forms_enabled()) rc_lcb = build_long_cb_device(p, st.rp, *st.dev(), st.in_lcb, st.slots(), st.lcb_pieces);
+    if (st.dev() && rc_lcb == kDevNoScratch) { if (int rc = fetch_device_csr(p, *st.dev_in, st.fetched)) return rc; }
+    if (!st.dev()) rc_lcb = build_long_cb(p, st.rp, st.ci(), st.val(), st.in_lcb, st.slots());
+    if (rc_lcb == 1) st.in_lcb.clear();          // (a piece too long for the kernel's LDS slice: the rows stay in the panels)
+    else if (rc_lcb) return rc_lcb;
+    st.lap("long rows by column block");
+    return DASP_OK;
+}
+
+// ---- the row tiles' bound: the caller's (opt.row_tile_max; < 0: no tiles), else the precision's default -- or, over that default only, the A/B knob
+template <class T> static int row_tile_bound(PanelBuild<T> &st)
+{
+    const Plan &p = st.p;
     int rt_max = p.opt.row_tile_max == 0 ? (p.precision == 16 ? kRowTileAuto : kRowTileAuto64) : std::max(0, p.opt.row_tile_max);
     if (rt_max > kRowTileMax) { set_error("row_tile_max must be <= 32"); return DASP_ERR_ARG; }
     if (p.opt.row_tile_max == 0 && ab_knobs().row_tile_max >= 0) rt_max = std::min(kRowTileMax, ab_knobs().row_tile_max);      // A/B knob: only over "auto", never over a caller's choice
-    struct RowTiles { std::vector<int> ptr; std::vector<uint16_t> start; std::vector<uint64_t> mask; raw_vector<char> val; raw_vector<int> cid; std::vector<int> at; size_t cnt = 0; std::vector<uint32_t> map; };
-    std::vector<RowTiles> rt((size_t)P);
-    // from a panel's row LENGTHS in len[1 .. m] (len[i + 1] = row i): the tiles' tables; the rows taken get length 0 in len
-    auto cut_row_tiles = [&](RowTiles &R, int *len) {
-        const int tiles = ceil_div(m, kRowTile);
-        R.ptr.assign((size_t)tiles + 1, 0); R.start.assign((size_t)tiles * kRowTile, 0); R.mask.assign((size_t)tiles, 0); R.at.assign((size_t)m, -1);
-        long long run = 0;
-        for (int t = 0; t < tiles; ++t) {
-            int in_tile = 0;
-            for (int i = 0; i < kRowTile; ++i) {
-                const int j = t * kRowTile + i;
-                R.start[(size_t)j] = (uint16_t)in_tile;
-                if (j >= m) continue;
-                const int r = natural ? j : p.order[(size_t)j], L = len[(size_t)r + 1];
-                if (L > rt_max) continue;
-                R.mask[(size_t)t] |= uint64_t(1) << i;
-                if (L > 0) { R.at[(size_t)r] = (int)(run + in_tile); in_tile += L; len[(size_t)r + 1] = 0; }
-            }
-            run += in_tile;
-            R.ptr[(size_t)t + 1] = (int)run;
-        }
-        R.cnt = (size_t)run;
-    };
-    if (dev) {
-        if (int rc = devpack_panel_split_masked(p, *dev, bnd, P, rpP, devP, dev_keep, lcb_on ? in_lcb.data() : nullptr)) return rc;
-        if (rt_max > 0) {
-            // the split's row pointers -> lengths, cut, -> the pointers of what is left; the device moves the elements (devpack.hip)
-            parallel_for(P, threads, 1, [&](long long k0, long long k1) {
-                for (long long k = k0; k < k1; ++k) {
-                    int *q = rpP[k].data();
-                    for (int i = m; i > 0; --i) q[i] -= q[i - 1];
-                    cut_row_tiles(rt[(size_t)k], q);
-                    for (int i = 0; i < m; ++i) q[i + 1] += q[i];
-                }
-            });
-            // (the device moves each panel's elements in that panel's worker below, beside the other panels' builds)
-        }
-    } else {
+    st.rt_max = rt_max;
+    return DASP_OK;
+}
+
+// ---- a host CSR split by column range: count, cut the row tiles, prefix, scatter (row-parallel; the rows' internal order is kept)
+template <class T> static int split_host(PanelBuild<T> &st)
+{
+    const Plan &p = st.p;
+    const int *const rp = st.rp, *const ci = st.ci();
+    const T *const val = st.val();
+    const int P = st.P, m = st.m, threads = st.threads, rt_max = st.rt_max;
+    const Remap remap = st.remap;
+    const std::vector<int> &bnd = st.bnd;
+    const unsigned char *const in_lcb = st.lcb_on() ? st.in_lcb.data() : nullptr;          // a hub row is an empty row in every panel
+    auto &rpP = st.rpP; auto &ciP = st.ciP; auto &valP = st.valP; auto &srcP = st.srcP; auto &rt = st.rt;
     for (auto &v : rpP) v.assign((size_t)m + 1, 0);
     parallel_for(m, threads, 1 << 12, [&](long long b, long long e) {
         for (long long i = b; i < e; ++i) {
-            if (lcb_on && in_lcb[(size_t)i]) continue;          // an empty row in every panel
-            for (int j = rp[i]; j < rp[i + 1]; ++j) rpP[panel_of(remap(ci[j]))][i + 1]++;
+            if (in_lcb && in_lcb[(size_t)i]) continue;
+            for (int j = rp[i]; j < rp[i + 1]; ++j) rpP[panel_of(bnd, remap(ci[j]))][i + 1]++;
         }
     });
     parallel_for(P, threads, 1, [&](long long k0, long long k1) {
         for (long long k = k0; k < k1; ++k) {
             int *q = rpP[k].data();
-            if (rt_max > 0) cut_row_tiles(rt[(size_t)k], q);
+            if (rt_max > 0) cut_row_tiles(rt[(size_t)k], rt_max, st.order(), m, q);
             for (int i = 0; i < m; ++i) q[i + 1] += q[i];
         }
     });
@@ -2060,87 +2131,125 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
         std::vector<int> cur((size_t)P);
         std::vector<char> tiled((size_t)P);
         for (long long i = b; i < e; ++i) {
-            if (lcb_on && in_lcb[(size_t)i]) continue;
+            if (in_lcb && in_lcb[(size_t)i]) continue;
             for (int k = 0; k < P; ++k) { const int at = rt_max > 0 ? rt[(size_t)k].at[(size_t)i] : -1; tiled[k] = at >= 0; cur[k] = at >= 0 ? at : rpP[k][i]; }
             for (int j = rp[i]; j < rp[i + 1]; ++j) {
-                const int c = remap(ci[j]), k = panel_of(c), at = cur[k]++;
+                const int c = remap(ci[j]), k = panel_of(bnd, c), at = cur[k]++;
                 if (tiled[k]) { rt[(size_t)k].cid[(size_t)at] = c; reinterpret_cast<T *>(rt[(size_t)k].val.data())[at] = val[j]; }
                 else { ciP[k][at] = c; valP[k][at] = val[j]; }
                 if (p.value_map) (tiled[k] ? rt[(size_t)k].map[(size_t)at] : srcP[k][(size_t)at]) = map_entry(p, j);
             }
         }
     });
-    }
+    return DASP_OK;
+}
 
-    lap("split by column range");
+// ---- a device CSR split by column range: two kernels (devpack.hip), the sub-matrices stay on the GPU.  Row tiles: the split's row pointers -> lengths, cut, ->
+// the pointers of what is left; the device moves each panel's elements in that panel's worker (make_panel_plan), beside the other panels' builds
+template <class T> static int split_device(PanelBuild<T> &st)
+{
+    const int m = st.m, rt_max = st.rt_max;
+    if (int rc = devpack_panel_split_masked(st.p, *st.dev(), st.bnd, st.P, st.rpP, st.devP, st.dev_keep, st.lcb_on() ? st.in_lcb.data() : nullptr)) return rc;
+    if (rt_max <= 0) return DASP_OK;
+    parallel_for(st.P, st.threads, 1, [&](long long k0, long long k1) {
+        for (long long k = k0; k < k1; ++k) {
+            int *q = st.rpP[k].data();
+            for (int i = m; i > 0; --i) q[i] -= q[i - 1];
+            cut_row_tiles(st.rt[(size_t)k], rt_max, st.order(), m, q);
+            for (int i = 0; i < m; ++i) q[i + 1] += q[i];
+        }
+    });
+    return DASP_OK;
+}
+
+// ---- the plan of panel k, from its sub-CSR and its row tiles, with `each` host threads: st.built[k], or nothing for an empty panel.  DASP_OK or the error
+// (its text in the calling thread's last_error)
+template <class T> static int make_panel_plan(PanelBuild<T> &st, int k, int each)
+{
+    Plan &p = st.p;
+    const DevCsr *const dev = st.dev();
+    const int m = st.m, nnz_k = st.rpP[k][m];
+    RowTiles &R = st.rt[(size_t)k];
+    if (nnz_k == 0 && R.cnt == 0) return DASP_OK;         // an empty panel adds nothing
+    if (dev && st.rt_max > 0) {
+        if (int rc = devpack_row_tiles(p, st.devP[(size_t)k], st.rpP[(size_t)k], R.at, R.cnt, st.rt_keep[(size_t)k], &st.rt_dev[(size_t)k])) return rc;
+    }
+    std::unique_ptr<dasp_plan> h(new dasp_plan());
+    Plan &q = h->impl;
+    q.precision = p.precision; q.geo = p.geo; q.m = m; q.n = (int)st.xlen; q.nnz = nnz_k;
+    q.opt = p.opt;
+    q.opt.y_order = DASP_Y_NATURAL; q.opt.n_parts = 0; q.opt.part_bounds = nullptr; q.opt.part_stride = 0;
+    q.opt.col_panels = 1; q.opt.host_threads = each;
     const bool streams = (long long)p.nnz * (p.geo.vbytes + 4) > kStreamBytes;
-    p.panels.clear(); p.panel_bounds.clear();
-    // the panels are built side by side (their O(rows) classifier passes are serial), each with its share of the threads
-    std::vector<std::unique_ptr<dasp_plan>> built((size_t)P);
-    std::vector<int> rcs((size_t)P, DASP_OK);
-    std::vector<std::string> errs((size_t)P);
-    {
-        // device path too: a panel's O(rows) host stages overlap another panel's kernels and copies (ljournal-2008, 4 panels: 4 x 26 ms one after the other)
-        const int side = dev ? std::min(P, std::min(4, threads)) : std::min(P, threads), each = std::max(1, threads / side);
-        const int hip_device = dev ? devpack_current_device() : -1;
-        std::atomic<int> next{0};
-        std::vector<std::thread> workers;
-        auto work = [&] {
-                if (dev) devpack_use_device(hip_device);          // a new thread starts on device 0
-                for (int k = next++; k < P; k = next++) {
-                    const int nnz_k = rpP[k][m];
-                    RowTiles &R = rt[(size_t)k];
-                    if (nnz_k == 0 && R.cnt == 0) continue;         // an empty panel adds nothing
-                    if (dev && rt_max > 0) {
-                        rcs[k] = devpack_row_tiles(p, devP[(size_t)k], rpP[(size_t)k], R.at, R.cnt, rt_keep[(size_t)k], &rt_dev[(size_t)k]);
-                        if (rcs[k] != DASP_OK) { errs[k] = last_error_cstr(); continue; }
-                    }
-                    std::unique_ptr<dasp_plan> h(new dasp_plan());
-                    Plan &q = h->impl;
-                    q.precision = p.precision; q.geo = p.geo; q.m = m; q.n = (int)xlen; q.nnz = nnz_k;
-                    q.opt = p.opt;
-                    q.opt.y_order = DASP_Y_NATURAL; q.opt.n_parts = 0; q.opt.part_bounds = nullptr; q.opt.part_stride = 0;
-                    q.opt.col_panels = 1; q.opt.host_threads = each;
-                    if (q.opt.stream_policy == 0) q.opt.stream_policy = streams ? 2 : 1;   // the policy follows the whole matrix, not one panel
-                    q.dst_map = slot_of_row; q.panel = true;
-                    q.value_map = p.value_map; q.map_src = p.value_map && !dev ? srcP[k].data() : nullptr;      // (device panels: DevCsr::src)
-                    if (R.cnt > 0) {      // (a panel none of whose rows is short enough keeps no tiles at all)
-                        q.rt_max = rt_max; q.cnt_rt = R.cnt;
-                        q.rt_ptr.swap(R.ptr); q.rt_start.swap(R.start); q.rt_mask.swap(R.mask); q.rt_val.swap(R.val); q.rt_cid.swap(R.cid); q.rt_map.swap(R.map);
-                        q.opt.x_window = -1; q.opt.cid8 = -1;      // the tiles ride in the non-windowed kernel without one-byte ids (dasp_spmv_rt_kernel)
-                    }
-                    // f16 only: 2-byte stores are where the partial lines hurt (ljournal-2008-uniform 0.590 -> 0.559 ms, ljournal-2008 0.506 -> 0.503; powerlaw_1M f64 0.651 -> 0.654)
-                    if (!natural && p.precision == 16 && !ab_knobs().panel_row_scan) q.scan_order = p.order.data();      // (DASP_PANEL_ROW_SCAN: A/B knob, the r3 order)
-                    try { rcs[k] = build_dasp<T>(q, rpP[k].data(), dev ? nullptr : ciP[k].data(), dev ? nullptr : valP[k].data(), dev ? &devP[(size_t)k] : nullptr, false); }
-                    catch (const std::bad_alloc &) { rcs[k] = DASP_ERR_NOMEM; set_error("out of host memory"); }
-                    if (rcs[k] == DASP_OK && dev && q.cnt_rt > 0) rcs[k] = devpack_place_row_tiles(q, rt_dev[(size_t)k]);
-                    if (rcs[k] != DASP_OK) { errs[k] = last_error_cstr(); continue; }
-                    q.opt.host_threads = p.opt.host_threads; q.scan_order = nullptr; q.map_src = nullptr;
-                    {   // the tiles in the panel's counters
-                        dasp_stats_t &t = q.stats;
-                        t.row_tile_max = q.rt_max; t.n_row_tiles = (int)q.rt_mask.size(); t.row_tile_nnz = (long long)q.cnt_rt;
-                        t.n_workgroups += ceil_div(t.n_row_tiles, kWavesPerWG);
-                        t.data_X += (long long)q.cnt_rt * (p.geo.vbytes + 4) + (long long)t.n_row_tiles * (4 + 2 * kRowTile + 8);
-                    }
-                    std::vector<int>().swap(rpP[k]); raw_vector<int>().swap(ciP[k]); raw_vector<T>().swap(valP[k]); raw_vector<uint32_t>().swap(srcP[k]);
-                    built[k] = std::move(h);
-                }
-            };
-        for (int t = 0; t < side; ++t) workers.emplace_back(work);
-        for (auto &w : workers) w.join();
+    if (q.opt.stream_policy == 0) q.opt.stream_policy = streams ? 2 : 1;   // the policy follows the whole matrix, not one panel
+    q.dst_map = st.slot_of_row; q.panel = true;
+    q.value_map = p.value_map; q.map_src = p.value_map && !dev ? st.srcP[k].data() : nullptr;      // (device panels: DevCsr::src)
+    if (R.cnt > 0) {      // (a panel none of whose rows is short enough keeps no tiles at all)
+        q.rt_max = st.rt_max; q.cnt_rt = R.cnt;
+        q.rt_ptr.swap(R.ptr); q.rt_start.swap(R.start); q.rt_mask.swap(R.mask); q.rt_val.swap(R.val); q.rt_cid.swap(R.cid); q.rt_map.swap(R.map);
+        q.opt.x_window = -1; q.opt.cid8 = -1;      // the tiles ride in the non-windowed kernel without one-byte ids (dasp_spmv_rt_kernel)
     }
-    lap("panel plans");
-    for (int k = 0; k < P; ++k) {
-        if (rcs[k] != DASP_OK) { set_error(errs[k]); return rcs[k]; }
-        if (!built[k]) continue;
-        p.panels.push_back(std::move(built[k]));
-        p.panel_bounds.push_back(bnd[k]); p.panel_bounds.push_back(bnd[k + 1]);
+    // f16 only: 2-byte stores are where the partial lines hurt (ljournal-2008-uniform 0.590 -> 0.559 ms, ljournal-2008 0.506 -> 0.503; powerlaw_1M f64 0.651 -> 0.654)
+    if (!st.natural && p.precision == 16 && !ab_knobs().panel_row_scan) q.scan_order = p.order.data();      // (DASP_PANEL_ROW_SCAN: A/B knob, the r3 order)
+    int rc;
+    try { rc = build_dasp<T>(q, st.rpP[k].data(), dev ? nullptr : st.ciP[k].data(), dev ? nullptr : st.valP[k].data(), dev ? &st.devP[(size_t)k] : nullptr, false); }
+    catch (const std::bad_alloc &) { rc = DASP_ERR_NOMEM; set_error("out of host memory"); }
+    if (rc == DASP_OK && dev && q.cnt_rt > 0) rc = devpack_place_row_tiles(q, st.rt_dev[(size_t)k]);
+    if (rc != DASP_OK) return rc;
+    q.opt.host_threads = p.opt.host_threads; q.scan_order = nullptr; q.map_src = nullptr;
+    {   // the tiles in the panel's counters
+        dasp_stats_t &t = q.stats;
+        t.row_tile_max = q.rt_max; t.n_row_tiles = (int)q.rt_mask.size(); t.row_tile_nnz = (long long)q.cnt_rt;
+        t.n_workgroups += ceil_div(t.n_row_tiles, kWavesPerWG);
+        t.data_X += (long long)q.cnt_rt * (p.geo.vbytes + 4) + (long long)t.n_row_tiles * (4 + 2 * kRowTile + 8);
     }
+    std::vector<int>().swap(st.rpP[k]); raw_vector<int>().swap(st.ciP[k]); raw_vector<T>().swap(st.valP[k]); raw_vector<uint32_t>().swap(st.srcP[k]);
+    st.built[k] = std::move(h);
+    return DASP_OK;
+}
 
-    // native counters: sums over the panels (the classifier counters above stay those of the whole matrix)
+// ---- the panels' plans, built side by side (their O(rows) classifier passes are serial), each with its share of the threads.  Device path too: a panel's O(rows)
+// host stages overlap another panel's kernels and copies (ljournal-2008, 4 panels: 4 x 26 ms one after the other)
+template <class T> static void build_panel_plans(PanelBuild<T> &st)
+{
+    const bool dev = st.dev() != nullptr;
+    const int P = st.P, threads = st.threads;
+    const int side = dev ? std::min(P, std::min(4, threads)) : std::min(P, threads), each = std::max(1, threads / side);
+    const int hip_device = dev ? devpack_current_device() : -1;
+    std::atomic<int> next{0};
+    std::vector<std::thread> workers;
+    auto work = [&] {
+        if (dev) devpack_use_device(hip_device);          // a new thread starts on device 0
+        for (int k = next++; k < P; k = next++) {
+            st.rcs[k] = make_panel_plan(st, k, each);
+            if (st.rcs[k] != DASP_OK) st.errs[k] = last_error_cstr();
+        }
+    };
+    for (int t = 0; t < side; ++t) workers.emplace_back(work);
+    for (auto &w : workers) w.join();
+}
+
+// ---- the panels in column order into the parent: the first error wins, empty panels are skipped
+template <class T> static int collect_panels(PanelBuild<T> &st)
+{
+    Plan &p = st.p;
+    p.panels.clear(); p.panel_bounds.clear();
+    for (int k = 0; k < st.P; ++k) {
+        if (st.rcs[k] != DASP_OK) { set_error(st.errs[k]); return st.rcs[k]; }
+        if (!st.built[k]) continue;
+        p.panels.push_back(std::move(st.built[k]));
+        p.panel_bounds.push_back(st.bnd[k]); p.panel_bounds.push_back(st.bnd[k + 1]);
+    }
+    return DASP_OK;
+}
+
+// ---- the parent's native counters: sums over the panels (the classifier counters stay those of the whole matrix), then the hub rows'
+template <class T> static void sum_panel_counters(PanelBuild<T> &st)
+{
+    Plan &p = st.p;
     dasp_stats_t &s = p.stats;
     const long long vb = p.geo.vbytes;
-    const int K = (int)p.panels.size();
+    const int m = st.m, K = (int)p.panels.size();
     s.fill0_nnz_short = s.fill0_nnz_long = s.fill0_nnz_reg = 0;
     s.n_med_blocks = s.n_long_pieces = s.n_long_multi = s.n_short_tiles = s.n_workgroups = 0;
     s.x_window_on = s.n_windows = s.n_windows_lds = s.lds_bytes = s.row_window = s.cid16_on = s.x_window_hybrid = s.chunk_pairs = s.cid8_chunks = 0;
@@ -2162,22 +2271,41 @@ static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int
     }
     s.rate_fill0 = p.nnz > 0 ? (double)(stored - p.nnz) / p.nnz : 0.0;
     // packed panels + x once + every panel's partial y written and read back + y
-    s.data_X = dataX + xlen * vb + (long long)(2 * K + 1) * m * vb;
+    s.data_X = dataX + st.xlen * vb + (long long)(2 * K + 1) * m * vb;
     s.n_col_panels = K;
-    if (lcb_on) {
-        const LongCB &L = p.lcb;
-        s.lcb_rows = L.n_rows(); s.lcb_elems = (long long)L.elems; s.lcb_col_block = L.cb; s.lcb_units = L.n_units();
-        s.n_workgroups += L.n_units() + ceil_div(L.n_rows(), kWavesPerWG);
-        stored += (long long)L.elems;
-        s.rate_fill0 = p.nnz > 0 ? (double)(stored - p.nnz) / p.nnz : 0.0;
-        // values + local columns streamed, every unit's slice of x, the partials written and read
-        s.data_X += (long long)L.elems * (vb + 2) + (long long)L.n_units() * std::min<long long>(L.cb, xlen) * vb + 2ll * L.n_cb * L.n_rows() * 8;
-    }
-    // a device-built plan comes back uploaded: the parent's partial-result buffers too, and the hub rows' streams written behind them
-    if (dev && lcb_on) { if (int rc = devpack_finish_panels_lcb(p, *dev, lcb_pieces)) return rc; }
-    else if (dev_in) { if (int rc = devpack_finish_panels(p)) return rc; }
-    lap("parent upload");
-    s.pre_ms = lap.ms();
+    if (st.lcb_on()) lcb_counters(p, st.xlen, &stored);
+}
+
+// ---- a device-built plan comes back uploaded: the parent's partial-result buffers too, and the hub rows' streams written behind them.  (A device CSR that the hub
+// rows' fallback fetched was packed by the host, but its plan comes back uploaded like any other.)
+template <class T> static int upload_parent(PanelBuild<T> &st)
+{
+    if (st.dev() && st.lcb_on()) return devpack_finish_panels_lcb(st.p, *st.dev(), st.lcb_pieces);
+    if (st.dev_in) return devpack_finish_panels(st.p);
+    return DASP_OK;
+}
+
+template <class T>
+static int build_panels(Plan &p, const int *rp, const int *ci, const T *val, int P, const DevCsr *dev)
+{
+    PanelBuild<T> st(p, rp, ci, val, P, dev);
+    // whole-matrix classification: order_rid and the reference's counters are those of the unsplit matrix (row lengths only)
+    if (int rc = build_dasp<T>(p, rp, ci, val, nullptr, true)) return rc;
+    st.lap("whole-matrix meta");
+    panel_bounds(st);
+    slot_table(p, st.slot_of_row);
+    st.lap("slot table");
+    if (int rc = hub_rows_leave_panels(st)) return rc;
+    if (int rc = row_tile_bound(st)) return rc;
+    if (int rc = st.dev() ? split_device(st) : split_host(st)) return rc;
+    st.lap("split by column range");
+    build_panel_plans(st);
+    st.lap("panel plans");
+    if (int rc = collect_panels(st)) return rc;
+    sum_panel_counters(st);
+    if (int rc = upload_parent(st)) return rc;
+    st.lap("parent upload");
+    p.stats.pre_ms = st.lap.ms();
     return DASP_OK;
 }
 

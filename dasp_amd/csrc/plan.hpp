@@ -447,10 +447,8 @@ int devpack_current_device();
 void devpack_use_device(int device);
 // remapped column ids at the nonzero positions idx[] (or start + i * stride for i < count when idx is null), copied to the host
 int devpack_gather_columns(const Plan &p, const DevCsr &d, const std::vector<long long> *idx, long long start, long long stride, long long count, std::vector<int> &out);      // uploads the parent of device-built panels (its partial-result buffers)
-// column-panel split of a device CSR: P sub-matrices by column range (remapped columns, row order kept); `keep` owns the device arrays
-int devpack_panel_split(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
-                        std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep);
-// the same with a row mask (nullptr: none): mask[row] != 0 = the row is empty in every panel (the hub rows of Plan::lcb)
+// column-panel split of a device CSR: P sub-matrices by column range (remapped columns, row order kept); `keep` owns the device arrays.
+// A row mask (nullptr: none): mask[row] != 0 = the row is empty in every panel (the hub rows of Plan::lcb)
 int devpack_panel_split_masked(const Plan &p, const DevCsr &d, const std::vector<int> &bnd, int P, std::vector<std::vector<int>> &rpP_host,
                                std::vector<DevCsr> &out, std::vector<std::shared_ptr<void>> &keep, const unsigned char *mask);
 

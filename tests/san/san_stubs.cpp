@@ -34,7 +34,6 @@ int devpack_fetch_csr(const Plan &, const DevCsr &, int *, void *) { return node
 int devpack_current_device() { return -1; }
 void devpack_use_device(int) {}
 int devpack_gather_columns(const Plan &, const DevCsr &, const std::vector<long long> *, long long, long long, long long, std::vector<int> &) { return nodev(); }
-int devpack_panel_split(const Plan &, const DevCsr &, const std::vector<int> &, int, std::vector<std::vector<int>> &, std::vector<DevCsr> &, std::vector<std::shared_ptr<void>> &) { return nodev(); }
 int devpack_row_tiles(const Plan &, DevCsr &, const std::vector<int> &, const std::vector<int> &, size_t, std::vector<std::shared_ptr<void>> &, DevRowTiles *) { return nodev(); }
 int devpack_place_row_tiles(Plan &, const DevRowTiles &) { return nodev(); }
 int devpack_sort_columns(const Plan &, const DevCsr &, std::vector<std::shared_ptr<void>> &, DevCsr *, int *) { return nodev(); }

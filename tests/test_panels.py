@@ -72,6 +72,52 @@ def test_panels_partition_the_matrix(dasp, prec, y_order, P, tile, lcb):
     assert plan.stats["row_tile_nnz"] == sum(plan.panel(k)[0].stats["row_tile_nnz"] for k in range(P))
 
 
+# every name dasp_plan_host_array answers to
+HOST_ARRAYS = ("order dst_map long_val long_cid long_cid16 long_base piece_c16 piece_ptr piece_dst multi_ptr multi_dst med_ptr med_val med_cid irr_ptr irr_val irr_cid "
+               "med_cid16 med_cid8 med_c8ptr med_korig med_base med_dst win_cmin win_len short_val short_cid rt_val rt_cid rt_ptr rt_start rt_mask "
+               "lcb_row_dst lcb_row_id lcb_ptr lcb_unit lcb_val lcb_lcol tp_rb_row0 tp_rb_seg0 tp_unit tp_dst tp_val tp_lrow tp_lcol short_groups "
+               "long_val_map med_val_map irr_val_map short_val_map rt_val_map tp_val_map lcb_val_map").split()
+LCB_ARRAYS = ("lcb_row_dst", "lcb_row_id", "lcb_ptr", "lcb_unit", "lcb_val", "lcb_lcol", "lcb_val_map")
+
+
+def stats_without_time(plan):
+    st = dict(plan.stats)
+    st.pop("pre_ms")      # wall time
+    return st
+
+
+@pytest.mark.parametrize("prec", [64, 16])
+@pytest.mark.parametrize("y_order", [0, 1])
+def test_panel_plan_does_not_depend_on_host_threads(dasp, prec, y_order):
+    """the panels are built side by side by a pool whose size follows host_threads, each with its share of the threads: what comes out -- the parent's order, counters
+    and hub rows, every panel's bounds, counters and arrays -- is the plan of one thread, byte for byte"""
+    dt = np.float64 if prec == 64 else np.float16
+    m, n = 1500, 5000
+    lens = np.random.default_rng(3).choice([0, 1, 2, 3, 4, 9, 40, 300, 700], size=m, p=[.05, .15, .1, .15, .1, .2, .15, .07, .03])
+    rp, ci, v = util.csr_from_lengths(lens, n, 5, dtype=dt)
+
+    def build(threads):
+        return dasp.Plan(rp, ci, v, n, precision=prec, y_order=y_order, col_panels=3, row_tile_max=5, long_cb=1, value_map=1, host_threads=threads)
+
+    one = build(1)
+    assert one.stats["lcb_rows"] > 0 and one.stats["row_tile_nnz"] > 0 and one.n_panels == 3 and one.host_array("lcb_val_map").size > 0
+    for threads in (3, 8):
+        other = build(threads)
+        np.testing.assert_array_equal(other.order_rid, one.order_rid)
+        assert stats_without_time(other) == stats_without_time(one)
+        for name in LCB_ARRAYS:
+            a, b = one.host_array(name), other.host_array(name)
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (threads, name)
+        assert other.n_panels == one.n_panels
+        for k in range(one.n_panels):
+            (pa, ba, ea), (pb, bb, eb) = one.panel(k), other.panel(k)
+            assert (ba, ea) == (bb, eb)
+            assert stats_without_time(pa) == stats_without_time(pb), (threads, k)
+            for name in HOST_ARRAYS:
+                a, b = pa.host_array(name), pb.host_array(name)
+                assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (threads, k, name)
+
+
 def test_empty_panels_are_dropped_and_auto_stays_off_for_small_inputs(dasp):
     rp, ci, v = util.mixed_matrix(800, 1000, 4)
     ci = (ci % 400).astype(np.int32)                       # nothing in the upper columns

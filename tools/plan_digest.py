@@ -2,8 +2,8 @@
 """tools/plan_digest.py [--list] -- one SHA-256 per host-built plan (and per panel of a panel parent) over a fixed case list: order_rid, every array
 dasp_plan_host_array knows, and the stats without pre_ms (wall time).  No GPU.  Two builds of the library pack the same plans exactly when their outputs are
 equal line for line:  python tools/plan_digest.py > new.txt; DASP_AMD_SO=dasp_amd/variants/<tag>/libdasp_amd.so python tools/plan_digest.py > old.txt
-(tools/build_rev.sh builds another revision).  Every case is built with host_threads = 1 and = 8; a line 'THREADS DIFFER' marks a case whose two digests
-are not equal, 'DROPPED' one the library rejects with an argument error (the last line counts both)."""
+(tools/build_rev.sh builds another revision).  Every case is built with host_threads = 1, 3 and 8; a line 'THREADS DIFFER' marks a case whose digests
+are not all equal, 'DROPPED' one the library rejects with an argument error (the last line counts both)."""
 import hashlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,6 +25,7 @@ SCALES = {"cop20k_A": 0.3, "nlpkkt160": 0.004, "powerlaw_1M": 0.01, "webbase-1M"
 # ... and, with the default options only, four of them at 17-27 M nonzeros: where the automatic rules for column panels, the two-phase form and the
 # window samples start to look at the matrix
 LARGE = {"rmat_2M": 0.6, "HV15R": 0.06, "ljournal-2008": 0.25, "powerlaw_1M": 0.3}
+THREADS = (1, 3, 8)      # host_threads of every case
 
 
 def synth_values(nnz, dt):
@@ -62,10 +63,15 @@ def option_sets(n, prec, large):
     if large:
         return [("default", {})]
     third = np.array([0, n // 3, 2 * n // 3, n], np.int32)
+    stride = (int(np.diff(third).max()) + 63) // 64 * 64
     sets = [("default", {}), ("threshold", dict(threshold=0.5, block_longest=64)), ("window", dict(x_window=81920, row_window=128)), ("window_order", dict(x_window=-2)),
             ("panels2", dict(col_panels=2)), ("slab_piece", dict(slab_max_len=12, piece_min_len=100)), ("cid8", dict(cid8=1)), ("short_seg", dict(short_seg=1)),
             ("sort_columns", dict(sort_columns=1)), ("value_map", dict(value_map=1)),
-            ("natural", dict(y_order=D.Y_NATURAL)), ("parts3", dict(part_bounds=third, part_stride=(int(np.diff(third).max()) + 63) // 64 * 64))]
+            ("natural", dict(y_order=D.Y_NATURAL)), ("parts3", dict(part_bounds=third, part_stride=stride)),
+            # column panels: hub rows by rule / forced / off, row tiles off / narrow / at their bound, empty panels dropped (tiny), the remap of a partitioned x, the value map
+            ("panels3_no_tiles", dict(col_panels=3, row_tile_max=-1, long_cb=-1)), ("panels7_tiles5_lcb", dict(col_panels=7, row_tile_max=5, long_cb=1)),
+            ("panels3_tiles32", dict(col_panels=3, row_tile_max=32, long_cb=0)), ("panels3_natural_map_lcb", dict(col_panels=3, y_order=D.Y_NATURAL, value_map=1, long_cb=1)),
+            ("panels3_parts3", dict(col_panels=3, part_bounds=third, part_stride=stride)), ("panels2_sorted_map", dict(col_panels=2, sort_columns=1, value_map=1))]
     if prec == 16:      # (the two-phase form is an f16 form: an f64 plan that asks for it is an argument error)
         sets += [("two_phase", dict(two_phase=1)), ("two_phase_lcb", dict(two_phase=1, long_cb=1))]
     return sets
@@ -102,7 +108,7 @@ def main():
                     print(label, rp.size - 1, ci.size)
                     continue
                 per_threads = []
-                for threads in (1, 8):
+                for threads in THREADS:
                     try:
                         plan = D.Plan(rp, ci, v, n, precision=prec, host_threads=threads, **opts)
                     except _lib.DaspError as err:
@@ -114,14 +120,15 @@ def main():
                 if per_threads[0].startswith("DROPPED"):
                     dropped += 1
                     dropped_sets[oname] = dropped_sets.get(oname, 0) + 1
-                elif per_threads[0] != per_threads[1]:
+                elif any(d != per_threads[0] for d in per_threads[1:]):
                     differ += 1
                     print(label, "THREADS DIFFER")
                 print(label, per_threads[0])
-                if per_threads[0] != per_threads[1]:
-                    print(label, "(8 threads)", per_threads[1])
+                for threads, d in zip(THREADS[1:], per_threads[1:]):
+                    if d != per_threads[0]:
+                        print(label, "(%d threads)" % threads, d)
     if "--list" not in sys.argv:
-        print("# %d cases (each with 1 and 8 host threads), %d dropped %s, %d differ between thread counts" % (cases, dropped, dropped_sets, differ))
+        print("# %d cases (each with 1, 3 and 8 host threads), %d dropped %s, %d differ between thread counts" % (cases, dropped, dropped_sets, differ))
     return 1 if differ else 0
 
 
