@@ -189,6 +189,9 @@ def lib():
         L.dasp_debug_spmv_variant.restype = C.c_char_p
         L.dasp_debug_plan_kernel.argtypes = [vp]
         L.dasp_debug_plan_kernel.restype = C.c_char_p
+        if hasattr(L, "dasp_debug_plan_panels_kernel"):      # (a library between the two revisions has the first hook only)
+            L.dasp_debug_plan_panels_kernel.argtypes = [vp]
+            L.dasp_debug_plan_panels_kernel.restype = C.c_char_p
     if hasattr(L, "dasp_debug_plan_launch_shape"):   # (likewise; test hooks of launch_shape.cpp and kernels.hip)
         L.dasp_debug_plan_launch_shape.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int]
         L.dasp_debug_f16_resident.argtypes = [C.c_int]

@@ -333,6 +333,14 @@ class Plan:
             raise _lib.DaspError(-22, _lib.lib().dasp_last_error().decode("utf-8", "replace"))
         return name.decode()
 
+    def panels_kernel(self):
+        """What an uploaded column-panel parent launches for its panels now: the merged kernel's name in the spelling of tools/isa_report.py (e.g.
+        `dasp_spmv_panels_kernel<double,0,1>`), or "per-panel" where every panel is launched by itself (ask each panel's kernel_variant())."""
+        name = _lib.lib().dasp_debug_plan_panels_kernel(self._h)
+        if name is None:
+            raise _lib.DaspError(-22, _lib.lib().dasp_last_error().decode("utf-8", "replace"))
+        return name.decode()
+
     def launch_shape(self, cus=256, f16_resident=0, uploaded=False):
         """The plan's launch shape (launch_shape.cpp) as a list of ints in the order of SHAPE_FIELDS.  uploaded=False: what an upload on a
         device of `cus` compute units holding `f16_resident` workgroups of the f16 kernel per CU (0: unknown) would decide now, environment knobs included -- no

@@ -1077,22 +1077,35 @@ int tp_kernels_allow_lds()
     return DASP_OK;
 }
 
-// the panels of a column-panel plan in one launch (+ one stage-2 launch when some panel cut a long row).  DASP_OK, an error, or 1 when the panels
-// cannot share one instantiation of the kernel (windows, one-byte ids, mixed id widths, more than kMaxMergedPanels) or DASP_PANELS_MERGED=0 asks for the old form
+// ---- how a column-panel parent launches its panels: pure host logic, no HIP call, nothing launched.  The kPanelVariants row all panels share (one merged launch), or null:
+// one launch per panel -- the panels cannot share one instantiation of the kernel (windows, one-byte ids, mixed id widths, more than kMaxMergedPanels) or
+// DASP_PANELS_MERGED=0 asks for the old form.  Asked by the launch and by the test hook dasp_debug_plan_panels_kernel
+static const Variant<PanelCall> *select_panels_variant(const Plan &p)
+{
+    static const bool off = [] { const char *e = std::getenv("DASP_PANELS_MERGED"); return e && std::atoi(e) == 0; }();      // A/B knob
+    if (off || p.panels.empty() || p.panels.size() > (size_t)kMaxMergedPanels) return nullptr;
+    const Plan &p0 = p.panels[0]->impl;
+    for (const auto &h : p.panels) {
+        const Plan &q = h->impl;
+        if (!q.dev || !q.dev->arena || q.windowed || q.two_phase || !q.panels.empty() || q.cnt_reg8 > 0 || q.cid16 != p0.cid16 || q.dev->nt != p0.dev->nt || q.dev->args.med_stride != p0.dev->args.med_stride) return nullptr;
+    }
+    return &find_variant(kPanelVariants, p.precision == 64 ? 64 : 16, (p0.dev->nt ? kVNt : 0u) | (p0.cid16 ? kVC16 : 0u) | kVRt);
+}
+
+// the panels of a column-panel plan in one launch (+ one stage-2 launch when some panel cut a long row).  DASP_OK, an error, or 1 when select_panels_variant says
+// one launch per panel
 template <class T>
 static int launch_panels_merged(Plan &p, const void *dX, char *part, size_t stride_bytes, hipStream_t s)
 {
-    static const bool off = [] { const char *e = std::getenv("DASP_PANELS_MERGED"); return e && std::atoi(e) == 0; }();      // A/B knob
-    if (off || p.panels.size() > (size_t)kMaxMergedPanels) return 1;
+    const Variant<PanelCall> *merged = select_panels_variant(p);
+    if (!merged) return 1;
     const int np = (int)p.panels.size();
     PanelCall c{};
     c.x = dX; c.part = part; c.stride_bytes = stride_bytes; c.np = np;
     PanelCall r = c;
     int grid = 0, grid2 = 0, rt_max = 0;
-    const Plan &p0 = p.panels[0]->impl;
     for (int k = 0; k < np; ++k) {
         Plan &q = p.panels[(size_t)k]->impl;
-        if (!q.dev || !q.dev->arena || q.windowed || q.two_phase || !q.panels.empty() || q.cnt_reg8 > 0 || q.cid16 != p0.cid16 || q.dev->nt != p0.dev->nt || q.dev->args.med_stride != p0.dev->args.med_stride) return 1;
         if (int rc = sync_dev_args(q)) return rc;
         const DevArgs &a = q.dev->args;
         grid += a.wg_long + a.wg_med + a.wg_short + a.wg_rt;
@@ -1102,8 +1115,7 @@ static int launch_panels_merged(Plan &p, const void *dX, char *part, size_t stri
         r.plan[k] = c.plan[k]; r.wg_end[k] = grid2;
     }
     const size_t lds = (size_t)kWavesPerWG * kRowTile * (size_t)rt_max * sizeof(typename Tr<T>::part_t);
-    const bool nt = p0.dev->nt, c16 = p0.cid16;
-    if (grid > 0) hipLaunchKernelGGL(find_variant(kPanelVariants, (int)sizeof(T) * 8, (nt ? kVNt : 0u) | (c16 ? kVC16 : 0u) | kVRt).fn, dim3(grid), dim3(256), lds, s, c);
+    if (grid > 0) hipLaunchKernelGGL(merged->fn, dim3(grid), dim3(256), lds, s, c);
     if (grid2 > 0) hipLaunchKernelGGL((dasp_long_reduce_panels_kernel<T>), dim3(grid2), dim3(256), 0, s, r);
     HIP_TRY(hipGetLastError());
     return DASP_OK;
@@ -1253,6 +1265,15 @@ extern "C" const char *dasp_debug_plan_kernel(const dasp_plan_t *plan)
     const dasp::Plan &p = plan->impl;
     const dasp::DevArgs &a = p.dev->args;
     return p.two_phase ? "two_phase" : !p.panels.empty() ? "panels" : a.wg_long + a.wg_med + a.wg_short + a.wg_rt > 0 ? dasp::select_spmv_variant(dasp::variant_key(p, *p.dev)).name : "none";
+}
+// what launch_panels would launch for the panels of this column-panel parent now: the merged variant's name (a kPanelVariants row) or "per-panel" (every panel by itself:
+// ask each for its dasp_debug_plan_kernel); null + the error text for a plan that is not an uploaded column-panel parent
+extern "C" const char *dasp_debug_plan_panels_kernel(const dasp_plan_t *plan)
+{
+    if (!plan || !plan->impl.dev || !plan->impl.dev->arena) { dasp::set_error("plan not uploaded"); return nullptr; }
+    if (plan->impl.panels.empty()) { dasp::set_error("not a column-panel parent"); return nullptr; }
+    const auto *v = dasp::select_panels_variant(plan->impl);
+    return v ? v->name : "per-panel";
 }
 // the second device fact behind a plan's launch shape (launch_shape.cpp DeviceFacts::f16_resident), as upload asks for it; needs a device
 extern "C" int dasp_debug_f16_resident(int c16) { return dasp::spmv_kernel_f16_resident(c16 != 0); }

@@ -227,7 +227,11 @@ def pattern(name):
         p = (rp, shuffled_rows(rp, ci, 5), 2500)
     elif name == "twins":
         p = twin_pattern()
-    elif name.startswith("short_tiles"):                 # rows of 1..4 nonzeros, `tiles` 64-element tiles (the last one partial) of every length
+    elif name == "pair_hand":                            # twin rows made of RUNS of adjacent columns: the pair mask of their shared id plane has set bits (`twins` has none)
+        import test_pair_gather
+        rp, ci, _, _ = test_pair_gather.hand_matrix()
+        p = (rp, ci, test_pair_gather.N_COLS)
+    elif name.startswith("short_tiles"):                # rows of 1..4 nonzeros, `tiles` 64-element tiles (the last one partial) of every length
         tiles = int(name[len("short_tiles"):])
         rng = np.random.default_rng(tiles)
         per_tile = {1: 64, 2: 32, 3: 20, 4: 16}

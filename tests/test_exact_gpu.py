@@ -441,12 +441,18 @@ def test_forms_that_meet(dasp, torch_cuda, tag, prec):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the multi-GPU step
-@pytest.mark.parametrize("prec,fused", [(64, True), (64, False), (16, False)])
-def test_multi_gpu_step_three_ranks_on_one_device(dasp, torch_cuda, prec, fused):
+MG_FORMS = [(64, True), (64, False), (16, False)]
+
+
+@pytest.mark.parametrize("prec,fused,stream_policy", [pytest.param(p, f, 1, id="%d-%s" % (p, f)) for p, f in MG_FORMS] + [pytest.param(p, f, 2, id="%d-%s-nt" % (p, f)) for p, f in MG_FORMS])
+def test_multi_gpu_step_three_ranks_on_one_device(dasp, torch_cuda, prec, fused, stream_policy):
     """three ranks' plans in one process on one device, the test-hook exchange copying every slice into every rank's gather buffer: ONE product, every
     rank's gathered y equals the exact y.  f64 in the fused one-launch form and in the two-launch form (y = own columns; y += other columns); an f16 plan
-    has the two-launch form only (its y is an f16 intermediate over the rank's own column range) and must say so."""
+    has the two-launch form only (its y is an f16 intermediate over the rank's own column range) and must say so.  stream_policy 1 / 2: plain / non-temporal
+    loads of the matrix (the automatic rule gives plain loads to plans this small) -- 2 runs dasp_mg_step_kernel<1> in the fused form and the NT = 1 builds of
+    both sub-plans in the two-launch form."""
     from dasp_amd.multi import MgPlan
+    import variant_cases as V
     torch = torch_cuda
     name, world = "mixed_square", 3
     rp, ci, n = X.pattern(name)
@@ -459,9 +465,11 @@ def test_multi_gpu_step_three_ranks_on_one_device(dasp, torch_cuda, prec, fused)
             mgs = []
             for r in range(world):
                 r0, r1 = int(bounds[r]), int(bounds[r + 1])
-                mgs.append(MgPlan(rp[r0:r1 + 1] - rp[r0], ci[rp[r0]:rp[r1]], a2[rp[r0]:rp[r1]], m, n, bounds, r, precision=prec, cid16=1, x_window=-1, col_panels=-1).upload())
+                mgs.append(MgPlan(rp[r0:r1 + 1] - rp[r0], ci[rp[r0]:rp[r1]], a2[rp[r0]:rp[r1]], m, n, bounds, r, precision=prec, cid16=1, x_window=-1, col_panels=-1, stream_policy=stream_policy).upload())
             for mg in mgs:
                 assert mg.overlap and mg.subplan(1) is not None and mg.nnz_local > 0 and mg.nnz_remote > 0
+                for which in (0, 1):
+                    assert V.shape_field(dasp, mg.subplan(which).launch_shape(uploaded=True), "nt") == stream_policy - 1, (mg.rank, which)
                 assert mg.info["fused_step"] == (1 if prec == 64 else 0)
                 if prec == 64:
                     mg.set_fused(fused)
