@@ -274,7 +274,8 @@ class Plan:
     def shared_ids(self):
         """Shared column ids of twin rows (include/dasp_amd.h dasp_plan_shared_ids), no GPU needed: a dict with `available` (the plan has a shared id
         plane), `paired_id_bytes` (id bytes streamed for the paired regions without it), `shared_bytes` (plane + table) and `in_use` (the uploaded plan
-        launches the kernel that reads it)."""
+        launches the kernel that reads it).  A plan from `from_device` reports what its creation derived on the GPU (nothing, hence `available` False, where the
+        plane was not wanted then: the plan does not stream from HBM and DASP_SHARE_IDS was not 1; or under DASP_DEVPACK_SHARED=0)."""
         pb, sb, use = C.c_longlong(0), C.c_longlong(0), C.c_int(0)
         rc = _lib.lib().dasp_plan_shared_ids(self._h, C.byref(pb), C.byref(sb), C.byref(use))
         if rc < 0:
@@ -283,7 +284,8 @@ class Plan:
 
     def shared_ids_export(self):
         """(plane, table) of the shared id plane as uint32 arrays; table has one row of four words per medium block: ranks of rows 0-7, ranks of rows 8-15
-        (4 bits each), offset into the plane in units of 16 bytes, number of distinct lists."""
+        (4 bits each), offset into the plane in units of 16 bytes, number of distinct lists.  A plan from `from_device` keeps the table on the host and the plane
+        on the device only: the plane is copied back where the plan carries one (`in_use`), and DaspError is raised where it does not."""
         out = []
         for what in (b"plane", b"table"):
             n = int(_lib.lib().dasp_plan_shared_ids_export(self._h, what, None, 0))
@@ -298,7 +300,8 @@ class Plan:
 
     def pair_mask(self):
         """The pair mask of the shared id plane (include/dasp_amd.h dasp_plan_pair_mask), no GPU needed: a dict with `available`, `words_per_block`,
-        `positions` (of all paired regions), `set_bits` (of the derived mask) and `set_bits_in_use` (of the mask the uploaded plan reads)."""
+        `positions` (of all paired regions), `set_bits` (of the derived mask) and `set_bits_in_use` (of the mask the uploaded plan reads).  A plan from
+        `from_device` answers from the mask its creation derived on the GPU and kept on the host."""
         w, pos, sb, use = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
         rc = _lib.lib().dasp_plan_pair_mask(self._h, C.byref(w), C.byref(pos), C.byref(sb), C.byref(use))
         if rc < 0:

@@ -338,6 +338,14 @@ int dasp_plan_shared_ids(const dasp_plan_t *plan, long long *paired_id_bytes, lo
     });
 }
 
+// the plane's tables and figures of any plan, without a GPU call: what devpack.hip derived for a plan packed on the device (Plan::sh_dev: no `plane`, that one lives on
+// the device), a derivation from the host id planes for every other.  Null: the plan has no plane
+static const SharedIds *shared_ids_of(const Plan &p, SharedIds &tmp)
+{
+    if (p.sh_dev) return p.sh_dev.get();
+    return derive_shared_ids(p, tmp) ? &tmp : nullptr;
+}
+
 long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what, void *dst, size_t bytes)
 {
     if (!plan || !what) return DASP_ERR_ARG;
@@ -345,9 +353,17 @@ long long dasp_plan_shared_ids_export(const dasp_plan_t *plan, const char *what,
     const int rc = guarded("dasp_plan_shared_ids_export", [&] {
         const bool plane = std::strcmp(what, "plane") == 0;
         if (!plane && std::strcmp(what, "table") != 0) { set_error("dasp_plan_shared_ids_export: \"plane\" or \"table\""); return (int)DASP_ERR_ARG; }
-        SharedIds sh;
-        if (!derive_shared_ids(plan->impl, sh)) { set_error("the plan has no shared id plane (f64 with 16-bit ids, host arrays present, at least one pipelined block)"); return (int)DASP_ERR_STATE; }
-        const std::vector<uint32_t> &v = plane ? sh.plane : sh.table;
+        const Plan &p = plan->impl;
+        if (plane && p.sh_dev) {      // packed on the device: the plane exists there only, and only where the launch reads it
+            if (!p.dev || !p.sh_in_use) { set_error("the plan was packed on the device and carries no shared id plane there (its launch does not read one): only the table and the pair mask were kept"); return (int)DASP_ERR_STATE; }
+            need = p.sh_dev->shared_bytes - (long long)p.sh_dev->table.size() * 4;
+            if (dst && bytes >= (size_t)need && need > 0) return download_array(const_cast<Plan &>(p), "med_shplane", dst, (size_t)need);
+            return (int)DASP_OK;
+        }
+        SharedIds tmp;
+        const SharedIds *sh = shared_ids_of(p, tmp);
+        if (!sh) { set_error("the plan has no shared id plane (f64 with 16-bit ids, at least one pipelined block; host arrays present, or derived when the plan was packed on the device)"); return (int)DASP_ERR_STATE; }
+        const std::vector<uint32_t> &v = plane ? sh->plane : sh->table;
         need = (long long)v.size() * 4;
         if (dst && bytes >= (size_t)need && need > 0) std::memcpy(dst, v.data(), (size_t)need);
         return (int)DASP_OK;
@@ -364,14 +380,15 @@ int dasp_plan_pair_mask(const dasp_plan_t *plan, int *words_per_block, long long
     if (set_bits) *set_bits = 0;
     if (set_bits_in_use) *set_bits_in_use = p.dev && p.sh_in_use ? p.pg_set : 0;
     return guarded("dasp_plan_pair_mask", [&] {
-        SharedIds sh;
-        if (!derive_shared_ids(p, sh)) return 0;
-        if (words_per_block) *words_per_block = sh.pm_words;
-        if (positions) *positions = sh.pair_positions;
-        if (set_bits) *set_bits = sh.pair_set;
+        SharedIds tmp;
+        const SharedIds *sh = shared_ids_of(p, tmp);
+        if (!sh) return 0;
+        if (words_per_block) *words_per_block = sh->pm_words;
+        if (positions) *positions = sh->pair_positions;
+        if (set_bits) *set_bits = sh->pair_set;
         // not uploaded: what an upload would place NOW (the rules of launch_shape.cpp and the two knobs, read as an upload reads them; no device needed)
         if (set_bits_in_use && !p.dev)
-            *set_bits_in_use = wants_shared_ids(p) && launch_shape(p, DeviceFacts{}, &sh).shared_ids && pair_gather_knob_allows() ? sh.pair_set : 0;
+            *set_bits_in_use = wants_shared_ids(p) && launch_shape(p, DeviceFacts{}, sh).shared_ids && pair_gather_knob_allows() ? sh->pair_set : 0;
         return 1;
     });
 }
@@ -381,10 +398,11 @@ long long dasp_plan_pair_mask_export(const dasp_plan_t *plan, void *dst, size_t 
     if (!plan) return DASP_ERR_ARG;
     long long need = 0;
     const int rc = guarded("dasp_plan_pair_mask_export", [&] {
-        SharedIds sh;
-        if (!derive_shared_ids(plan->impl, sh)) { set_error("the plan has no shared id plane, hence no pair mask (f64 with 16-bit ids, host arrays present, at least one pipelined block)"); return (int)DASP_ERR_STATE; }
-        need = (long long)sh.pair_mask.size() * 4;
-        if (dst && bytes >= (size_t)need && need > 0) std::memcpy(dst, sh.pair_mask.data(), (size_t)need);
+        SharedIds tmp;
+        const SharedIds *sh = shared_ids_of(plan->impl, tmp);
+        if (!sh) { set_error("the plan has no shared id plane, hence no pair mask (f64 with 16-bit ids, at least one pipelined block; host arrays present, or derived when the plan was packed on the device)"); return (int)DASP_ERR_STATE; }
+        need = (long long)sh->pair_mask.size() * 4;
+        if (dst && bytes >= (size_t)need && need > 0) std::memcpy(dst, sh->pair_mask.data(), (size_t)need);
         return (int)DASP_OK;
     });
     return rc != DASP_OK ? (long long)rc : need;

@@ -130,6 +130,9 @@ struct DevicePlan {
     // r7: the arena holds the shared id plane (DevArgs::med_shplane) and the launch uses the kernel that reads it (kernels.hip dasp_spmv_shared_kernel): f64 plans that stream
     // from HBM and whose twin rows save >= 3 % of the streamed bytes (launch_shape.cpp shared_ids_rule)
     bool shared_ids = false;
+    // a plan packed on the device that launches the shared kernel: plane, table and pair mask in ONE allocation of their own (devpack.hip devpack_shared_ids) -- the arena was
+    // sized before the packers ran and is byte for byte what it is without a plane.  Null for every other plan
+    void *sh_alloc = nullptr;
     // what DevArgs::ywt is at a launch, before the DASP_Y_WT knob (launch_shape.cpp).  Here and not in `args`: it follows nt, which dasp_plan_set_stream_policy may change
     // between two launches, and a changed `args` would be re-sent to the device by the next launch -- a blocking copy, possibly inside a stream capture
     bool ywt = false;

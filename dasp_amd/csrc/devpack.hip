@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "device.hpp"
+#include "sharedids_lane.hpp"
 
 namespace dasp {
 
@@ -1218,6 +1219,141 @@ int devpack_densest_spans(const Plan &p, const DevCsr &d, const raw_vector<int> 
     return DASP_OK;
 }
 
+// ---- the shared id plane of a plan packed here (plan.hpp struct SharedIds).  sharedids.cpp's derive_shared_ids, which reads the HOST copies of med_cid8 / med_cid16, is
+// the specification; these kernels read the same bytes where the packers above left them, in the arena, and write the same words.  One wave per medium block; a slot is
+// 64 id dwords (lane = row + 16 kq owns dword `lane`): the block's narrow batches, then its wide pairs.  Integer work in a fixed order, no atomics: nothing depends on the run
+namespace {
+
+struct ShBlock { const unsigned *narrow, *wide; int n8, slots8, slots; };
+// false: the block is one-shot or pairs nothing (an all-zero table entry, all-zero mask words)
+__device__ __forceinline__ bool sh_block(const DevArgs &a, int b, ShBlock &s)
+{
+    const int c0 = a.med_ptr[b], nc = a.med_ptr[b + 1] - c0, nt = a.med_nt[b];
+    if (med_oneshot64(nc, nt)) return false;
+    const int npair = med_npair(nc, nt, 8, a.pair_mode);
+    if (npair <= 0) return false;
+    const int q0 = a.med_c8ptr[b];
+    s.n8 = a.med_c8ptr[b + 1] - q0;
+    s.slots8 = s.n8 / kMedBatch64; s.slots = s.slots8 + (npair - s.n8) / 2;
+    s.narrow = reinterpret_cast<const unsigned *>(a.med_cid8 + (size_t)q0 * 64);
+    s.wide = reinterpret_cast<const unsigned *>(a.med_cid16 + (size_t)(c0 - q0) * 64);      // the block's wide chunks follow each other, pair by pair
+    return true;
+}
+__device__ __forceinline__ unsigned sh_load(const ShBlock &s, int t, int lane) { return t < s.slots8 ? s.narrow[(size_t)t * 64 + lane] : s.wide[(size_t)(t - s.slots8) * 64 + lane]; }
+
+// pass A: table[4b], [4b + 1] = the sixteen ranks, table[4b + 3] = L (the offset, [4b + 2], is the host's: finish_shared_ids); the block's words of the pair mask.  Both
+// buffers arrive zeroed
+__global__ void k_shared_ranks(DevArgs a, int nb, int two_cols, unsigned *table, unsigned *pmask, int pm_words)
+{
+    const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= nb) return;
+    ShBlock s;
+    if (!sh_block(a, b, s)) return;
+    const int row = lane & 15, kq = lane >> 4;
+    unsigned differs = 0, word = 0;
+    int wi = 0;
+    unsigned *const pm = pmask + (size_t)b * (size_t)pm_words;
+    for (int t = 0; t < s.slots; ++t) {
+        const bool narrow = t < s.slots8;
+        const unsigned dw = sh_load(s, t, lane);
+        for (int q = 0; q < kMedRows; ++q) differs |= (unsigned)(__shfl(dw, q + 16 * kq) != dw) << q;
+        // the pair mask: the even quarters judge their couple (kq | kq + 1), the odd ones agree with everything
+        const unsigned partner = __shfl_xor(dw, 16);
+        const int i0 = narrow ? kMedBatch64 * t : s.n8 + 2 * (t - s.slots8);
+        for (int j = 0; j < (narrow ? kMedBatch64 : 2); ++j) {
+            const int i = i0 + j;
+            if ((i >> 5) != wi) { if (lane == 0 && word) pm[wi] = word; word = 0; wi = i >> 5; }
+            if (__all((kq & 1) || sh_couple_ok(dw, partner, narrow, j, two_cols != 0))) word |= 1u << (i & 31);
+        }
+    }
+    if (lane == 0 && word) pm[wi] = word;
+    differs |= __shfl_xor(differs, 16); differs |= __shfl_xor(differs, 32);
+    const int rep = sh_rep_of(differs);
+    const unsigned reps = (unsigned)(__ballot(rep == row) & 0xFFFFull);
+    unsigned long long ranks = kq == 0 ? (unsigned long long)sh_rank_of(reps, rep) << (4 * row) : 0ull;
+    for (int o = 8; o; o >>= 1) ranks |= __shfl_xor(ranks, o);
+    if (lane == 0) { table[4 * (size_t)b] = (unsigned)ranks; table[4 * (size_t)b + 1] = (unsigned)(ranks >> 32); table[4 * (size_t)b + 3] = (unsigned)__popc(reps); }
+}
+
+// pass B: every list's dwords, once: the lanes of a list's first row write plane[offset + (slot * 4 + kq) * L + list]
+__global__ void k_shared_plane(DevArgs a, int nb, const unsigned *table, unsigned *plane)
+{
+    const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= nb) return;
+    ShBlock s;
+    if (!sh_block(a, b, s)) return;
+    const int row = lane & 15, kq = lane >> 4;
+    const unsigned *e = table + 4 * (size_t)b;
+    const unsigned long long ranks = (unsigned long long)e[0] | (unsigned long long)e[1] << 32;
+    const size_t L = e[3];
+    if (!sh_first_of_list(ranks, row)) return;
+    unsigned *dst = plane + (size_t)e[2] * 4 + (size_t)kq * L + (size_t)((ranks >> (4 * row)) & 15u);
+    for (int t = 0; t < s.slots; ++t) dst[(size_t)t * 4 * L] = sh_load(s, t, lane);
+}
+
+}  // namespace
+
+// DASP_DEVPACK_SHARED, read at every dasp_plan_create_device: "0" = no derivation, the plan is what it was before these kernels existed (the A/B knob); "noscratch" =
+// every allocation below "fails" (test hook of the fallback).  A failed allocation, scratch or plane, is not an error: the plan keeps the plain kernel
+int devpack_shared_ids(Plan &p)
+{
+    const char *const knob = std::getenv("DASP_DEVPACK_SHARED");
+    if (knob && std::strcmp(knob, "0") == 0) return DASP_OK;
+    if (!shared_ids_form_qualifies(p) || !wants_shared_ids(p)) return DASP_OK;
+    const bool refused = knob && std::strcmp(knob, "noscratch") == 0;
+    DevicePlan &dp = *p.dev;
+    const size_t nb = p.med_ptr.size() - 1;
+    const int pm_words = shared_ids_pm_words(p);
+    if (pm_words == 0 || (size_t)dp.args.n_blocks != nb) return DASP_OK;      // no paired region anywhere: no plane (what the upload recorded stands)
+    using clk = std::chrono::steady_clock;
+    const bool verbose = std::getenv("DASP_VERBOSE") != nullptr;
+    auto tick = clk::now();
+    auto lap = [&](const char *what) {
+        if (!verbose) return;
+        (void)hipDeviceSynchronize();
+        const auto now = clk::now();
+        std::fprintf(stderr, "[dasp shared] %-27s %.3f ms\n", what, 1e3 * std::chrono::duration<double>(now - tick).count());
+        tick = now;
+    };
+    FormScratch sc;
+    const size_t tab_bytes = nb * 16, pm_bytes = nb * (size_t)pm_words * 4;
+    auto *tab = refused ? nullptr : static_cast<unsigned *>(sc.get(tab_bytes));
+    auto *pm = refused ? nullptr : static_cast<unsigned *>(sc.get(pm_bytes));
+    if (!tab || !pm) return DASP_OK;
+    HIP_TRYP(hipMemset(tab, 0, tab_bytes));
+    HIP_TRYP(hipMemset(pm, 0, pm_bytes));
+    lap("scratch");
+    hipLaunchKernelGGL(k_shared_ranks, dim3(waves_grid((int)nb)), dim3(256), 0, 0, dp.args, (int)nb, p.n >= 2 ? 1 : 0, tab, pm, pm_words);
+    HIP_TRYP(hipGetLastError());
+    lap("ranks, L, pair mask");
+    auto sh = std::make_unique<SharedIds>();
+    sh->table.resize(4 * nb); sh->pair_mask.resize(nb * (size_t)pm_words); sh->pm_words = pm_words;
+    HIP_TRYP(hipMemcpy(sh->table.data(), tab, tab_bytes, hipMemcpyDeviceToHost));
+    HIP_TRYP(hipMemcpy(sh->pair_mask.data(), pm, pm_bytes, hipMemcpyDeviceToHost));
+    if (!finish_shared_ids(p, *sh)) return DASP_OK;
+    if (verbose) std::fprintf(stderr, "[dasp shared] scratch %zu bytes, plane + table %lld of %lld paired id bytes\n", tab_bytes + pm_bytes, sh->shared_bytes, sh->paired_id_bytes);
+    if (launch_shape(p, DeviceFacts{}, sh.get()).shared_ids) {
+        // plane, table and mask in ONE allocation of their own, laid out like the tail of a host-built plan's arena: the arena was sized before packing and stays what it is
+        auto round = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+        const size_t plane_bytes = (size_t)sh->shared_bytes - tab_bytes, o_tab = round(plane_bytes), o_pm = o_tab + round(tab_bytes), total = o_pm + round(pm_bytes);
+        char *own = refused ? nullptr : static_cast<char *>(sc.get(total));
+        if (!own) return DASP_OK;
+        HIP_TRYP(hipMemcpy(own + o_tab, sh->table.data(), tab_bytes, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_shared_plane, dim3(waves_grid((int)nb)), dim3(256), 0, 0, dp.args, (int)nb, reinterpret_cast<const unsigned *>(own + o_tab), reinterpret_cast<unsigned *>(own));
+        HIP_TRYP(hipGetLastError());
+        // DASP_PAIR_GATHER=0 (read here, as an upload reads it) places the mask all zero; the derived one stays with the plan
+        const bool pairs = pair_gather_knob_allows();
+        if (pairs) HIP_TRYP(hipMemcpy(own + o_pm, pm, pm_bytes, hipMemcpyDeviceToDevice));
+        else HIP_TRYP(hipMemset(own + o_pm, 0, pm_bytes));
+        HIP_TRYP(hipDeviceSynchronize());
+        lap("plane");
+        if (int rc = adopt_shared_plane(p, *sh, sc.release(own), o_tab, o_pm, pairs ? sh->pair_set : 0)) return rc;
+    }
+    p.sh_paired_bytes = sh->paired_id_bytes; p.sh_shared_bytes = sh->shared_bytes; p.sh_known = true;
+    p.sh_dev = std::move(sh);
+    return DASP_OK;
+}
+
 int devpack_current_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; } return d; }
 void devpack_use_device(int device) { if (device >= 0) (void)hipSetDevice(device); }
 
@@ -1228,6 +1364,8 @@ int devpack_all(Plan &p, const DevCsr &d, const PackMeta &m)
     // ... then the kernels above fill those regions straight from the device CSR
     const int rc = p.precision == 64 ? pack_all_typed<double>(p, d, m) : pack_all_typed<_Float16>(p, d, m);
     if (rc == DASP_OK) p.host_dropped = true;       // no host copies of the packed nonzeros exist
+    // ... and the shared id plane, which a host-built plan's upload derives from the host copies, from the id planes just written
+    if (rc == DASP_OK) if (int rs = devpack_shared_ids(p)) return rs;
     if (rc == DASP_OK && p.value_map && !p.panel) return value_map_upload(p);      // (a panel's maps go with its parent's: devpack_finish_panels)
     return rc;
 }
@@ -1529,6 +1667,12 @@ int download_array(Plan &p, const char *name, void *dst, size_t bytes)
     if (!p.dev || !p.dev->arena) { set_error("plan not on the device"); return DASP_ERR_STATE; }
     const ArenaMap &mp = p.dev->map;
     const size_t vb = (size_t)p.geo.vbytes;
+    if (std::strcmp(name, "med_shplane") == 0) {      // the shared id plane of a plan packed on the device: it exists there only (dasp_plan_shared_ids_export)
+        if (!p.sh_dev || !p.dev->sh_alloc) { set_error("the plan carries no shared id plane of its own on the device"); return DASP_ERR_STATE; }
+        if (bytes != (size_t)p.sh_dev->shared_bytes - p.sh_dev->table.size() * 4) { set_error("size mismatch for med_shplane"); return DASP_ERR_ARG; }
+        if (bytes) HIP_TRYP(hipMemcpy(dst, p.dev->sh_alloc, bytes, hipMemcpyDeviceToHost));
+        return DASP_OK;
+    }
     if (std::strcmp(name, "lcb_val") == 0 && p.dev->lcb.val) {      // column-blocked long rows of a column-panel parent or of a two-phase plan
         if (bytes != p.lcb.elems * vb) { set_error("size mismatch for lcb_val"); return DASP_ERR_ARG; }
         if (bytes) HIP_TRYP(hipMemcpy(dst, p.dev->lcb.val, bytes, hipMemcpyDeviceToHost));

@@ -235,11 +235,12 @@ extern "C" int dasp_debug_plan_launch_shape(const dasp_plan_t *plan, int cus, in
         s = shape_of(*p.dev);
     } else {
         SharedIds sh;
-        const bool have = p.two_phase || !p.panels.empty() ? false : wants_shared_ids(p) && derive_shared_ids(p, sh);
+        // (a plan packed on the device: the figures its creation stored -- the rule reads the two byte counts only)
+        const SharedIds *have = p.two_phase || !p.panels.empty() || !wants_shared_ids(p) ? nullptr : p.sh_dev ? p.sh_dev.get() : derive_shared_ids(p, sh) ? &sh : nullptr;
         DeviceFacts dev;
         if (cus > 0) dev.cus = cus;
         dev.f16_resident = f16_resident;
-        s = launch_shape(p, dev, have ? &sh : nullptr);
+        s = launch_shape(p, dev, have);
     }
     std::vector<int> v = {s.nt, s.win1, s.seven_waves, s.long16, s.shared_ids, s.wpw, s.wg_long, s.wg_med, s.wg_short, s.wg_rt, s.wg_rot, s.win_tiles, s.win_xcd, s.short_tpw, s.n_short_waves};
     v.insert(v.end(), s.grp_wave0, s.grp_wave0 + kNumShortGroups);

@@ -236,6 +236,7 @@ struct LongCB {
 };
 
 struct DevicePlan;  // kernels.hip
+struct SharedIds;   // below
 }  // namespace dasp
 struct dasp_plan;      // the C handle (defined at the end of this file): one Plan
 namespace dasp {
@@ -367,6 +368,10 @@ struct Plan {
     // r15: what the last upload put into the pair mask (SharedIds::pair_mask) -- positions of the paired regions and set bits IN USE (0 / 0 without a plane in the arena,
     // x / 0 under DASP_PAIR_GATHER=0): the `pair_gather_positions` figure of dasp_plan_pair_mask
     long long pg_positions = 0, pg_set = 0;
+    // a plan packed on the device has no host copy of the id planes: what devpack.hip's kernels derived from the arena (devpack_shared_ids) -- the table, the pair mask
+    // and every figure of struct SharedIds below, O(blocks) like the other tables such a plan keeps; `plane` stays empty (it lives on the device only, and only where
+    // the launch reads it: DevicePlan::sh_alloc).  Null for every other plan, and where nothing was derived (wants_shared_ids false at creation, DASP_DEVPACK_SHARED=0)
+    std::unique_ptr<SharedIds> sh_dev;
     DevicePlan *dev = nullptr;
 
     ~Plan();
@@ -393,8 +398,18 @@ struct SharedIds {
     int pm_words = 0;
     long long pair_positions = 0, pair_set = 0;      // positions of all paired regions, and how many of their bits are set
 };
-bool shared_ids_qualify(const Plan &p);                        // f64, 16-bit ids, no windows / panels / two-phase form, host id arrays present
+bool shared_ids_form_qualifies(const Plan &p);                 // f64, 16-bit ids, no windows / panels / two-phase form, at least one medium block
+bool shared_ids_qualify(const Plan &p);                        // ... and the host id arrays present
 bool derive_shared_ids(const Plan &p, SharedIds &out);         // false: the plan does not qualify or has no pipelined block (out is empty)
+// the derivation of a plan packed on the device (devpack.hip devpack_shared_ids), its host half: the words per block of the pair mask; and, once the kernels have left
+// every pipelined block's ranks and L in sh.table and its bits in sh.pair_mask, the blocks' offsets and every figure of sh but the plane -- derive_shared_ids' own
+// numbers for the same plan.  false: no pipelined block, or an offset that no longer fits its word (sh is empty)
+int shared_ids_pm_words(const Plan &p);
+bool finish_shared_ids(const Plan &p, SharedIds &sh);
+// devpack.hip: derives the plane of a plan it has just packed and, where the launch shape wants it, places it; a failed allocation leaves the plan without one (DASP_OK)
+int devpack_shared_ids(Plan &p);
+// upload.cpp: the plan launches the shared kernel over a plane in an allocation of its own (plane at 0, table at o_tab, pair mask at o_mask)
+int adopt_shared_plane(Plan &p, const SharedIds &sh, void *alloc, size_t o_tab, size_t o_mask, long long set_bits_placed);
 
 // ---- device-side packing (dasp_plan_create_device): the CSR stays on the GPU; the host keeps doing the O(rows) decisions
 // from the row pointer alone and hands the O(nnz) work to the kernels in devpack.hip through these hooks.

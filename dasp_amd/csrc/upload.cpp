@@ -32,6 +32,7 @@ Plan::~Plan()
     if (dev) {
         value_map_free(dev);
         if (dev->arena) (void)hipFree(dev->arena);
+        if (dev->sh_alloc) (void)hipFree(dev->sh_alloc);
         if (dev->lcb_xpart) (void)hipFree(dev->lcb_xpart);
         if (dev->wide_xs) (void)hipFree(dev->wide_xs);
         if (dev->wide_part) (void)hipFree(dev->wide_part);
@@ -107,6 +108,7 @@ void release_device(Plan &p)
 {
     if (p.dev) {
         value_map_free(p.dev); if (p.dev->arena) (void)hipFree(p.dev->arena); if (p.dev->lcb_xpart) (void)hipFree(p.dev->lcb_xpart);
+        if (p.dev->sh_alloc) (void)hipFree(p.dev->sh_alloc);
         if (p.dev->wide_xs) (void)hipFree(p.dev->wide_xs);
         if (p.dev->wide_part) (void)hipFree(p.dev->wide_part);
         if (p.dev->dargs) (void)hipFree(p.dev->dargs); std::free(p.dev->args_sent); delete p.dev; p.dev = nullptr;
@@ -356,6 +358,22 @@ static int upload_row_forms(Plan &p, DevicePlan *d)
         // windows would lower the limit under an earlier one with wider windows
         if (int rc = spmv_kernel_allow_full_lds(p.precision, p.cid16)) return rc;
     }
+    return sync_dev_args(p);
+}
+
+// a plan packed on the device whose plane devpack.hip has just derived and placed: wire the three pointers, decide the launch shape again with the plane's figures (the
+// same rules over the same numbers as a host-built plan's upload) and send the arguments
+int adopt_shared_plane(Plan &p, const SharedIds &sh, void *alloc, size_t o_tab, size_t o_mask, long long set_bits_placed)
+{
+    DevicePlan *d = p.dev;
+    d->sh_alloc = alloc;
+    const char *base = static_cast<const char *>(alloc);
+    DevArgs &a = d->args;
+    a.med_shplane = (const unsigned char *)base; a.med_shtab = (const unsigned *)(base + o_tab);
+    a.med_pmask = (const unsigned *)(base + o_mask); a.med_pm_words = sh.pm_words;
+    apply(launch_shape(p, device_facts(p, d->device), &sh), *d);
+    p.sh_in_use = d->shared_ids;
+    p.pg_positions = sh.pair_positions; p.pg_set = set_bits_placed;
     return sync_dev_args(p);
 }
 

@@ -299,7 +299,9 @@ int dasp_plan_create(dasp_plan_t **plan, int precision, int rowA, int colA, int 
  * as the fallback of those two forms only -- when the device packers' scratch (about 24 bytes per nonzero while they run) cannot be allocated, or
  * DASP_DEVPACK_FORMS=0 is set (read at every call): the column ids and values are then copied to the host once; dasp_plan_csr_fetch_bytes tells.  The
  * search of the hybrid windows has the same kind of fallback and a knob of its own: without room for its scratch, or under DASP_DEVPACK_HYBRID=0, the column ids
- * alone (4 bytes per nonzero) are copied to the host once and searched there. */
+ * alone (4 bytes per nonzero) are copied to the host once and searched there.  The shared id plane and the pair mask of an f64 plan (dasp_plan_shared_ids
+ * below) are derived on the device as well, from the packed ids, where an upload of the host-built plan would derive them: the same words, the same rule, the
+ * same kernel. */
 int dasp_plan_create_device(dasp_plan_t **plan, int precision, int rowA, int colA, int nnzA,
                             const int *dRowPtr, const int *dColIdx, const void *dVal, const dasp_options_t *opt);
 /* Placement trials (r3; opt-in since r4): the same packed bytes run the HBM-bound kernels at one of two speeds ~8 % apart depending on where the
@@ -369,7 +371,8 @@ long long dasp_plan_value_map_slots(const dasp_plan_t *plan);
  * host packers.  The bounded column samples of the automatic rules are not counted. */
 long long dasp_plan_csr_fetch_bytes(const dasp_plan_t *plan);
 
-/* Shared column ids of twin rows (f64 plans with 16-bit ids, no x windows, panels or two-phase form, host arrays present).  A mesh matrix with d unknowns
+/* Shared column ids of twin rows (f64 plans with 16-bit ids, no x windows, panels or two-phase form; packed on the host with the host arrays present, or packed
+ * on the device by dasp_plan_create_device -- see the last paragraph).  A mesh matrix with d unknowns
  * per node has d consecutive rows with one column list; inside the paired region of a pipelined medium block such rows store identical id bytes.  At
  * upload the library derives a plane that keeps each distinct list of a block once, and plans that stream from HBM and save >= 3 % of their streamed
  * bytes that way run the kernel that reads it (DASP_SHARE_IDS=1 / 0, read at upload: always where a plane exists / never; plans of one-shot blocks,
@@ -378,7 +381,14 @@ long long dasp_plan_csr_fetch_bytes(const dasp_plan_t *plan);
  * reach the same lanes.
  * dasp_plan_shared_ids answers without a GPU: *paired_id_bytes = id bytes the kernel streams for the paired regions today, *shared_bytes = plane + per-block
  * table, *in_use = 1 when the uploaded plan launches the shared kernel.  Returns 1 when the plan has such a plane, 0 when it has none (both sizes 0),
- * < 0 on error.  Any out pointer may be null. */
+ * < 0 on error.  Any out pointer may be null.
+ * A plan packed on the device (dasp_plan_create_device) has no host copy of its ids: where the plane is wanted when the plan is created -- it streams from HBM,
+ * or DASP_SHARE_IDS=1 -- kernels derive the same words from the packed ids on the device, the same rule decides, and a plan that launches the shared kernel keeps
+ * plane, table and mask in ONE device allocation of its own (the arena is byte for byte what it is without them).  The table, the pair mask and the figures stay
+ * with the plan on the host, and these four calls answer from them, still without a GPU call -- but for "plane" of dasp_plan_shared_ids_export, which is copied
+ * back from the device where the plan carries one and is DASP_ERR_STATE where it does not.  Nothing is derived later: a device-built plan for which the plane was
+ * not wanted at creation keeps answering 0.  A failed allocation of the derivation leaves a plan without a plane (DASP_OK), as does DASP_DEVPACK_SHARED=0, read
+ * at every dasp_plan_create_device (=noscratch: the test hook of that failure). */
 int dasp_plan_shared_ids(const dasp_plan_t *plan, long long *paired_id_bytes, long long *shared_bytes, int *in_use);
 /* copy out the plane (what = "plane": 32-bit words, per block its narrow batches then its wide pairs, [kq][list] inside each) or the table (what = "table":
  * four 32-bit words per medium block -- the sixteen 4-bit list numbers of its rows, low rows first, in two words; the block's offset into the plane in
